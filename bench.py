@@ -17,10 +17,15 @@ N > 1 (torch.distributed.run, one rank per GPU, RCCL) every rank decodes its own
 64 Ki-block shard (weak scaling) and each step also performs the offset concat:
 an all-gather of per-rank totals and the rebase of the per-block bases.
 
-Rank 0 prints ONE JSON line.  Extra objects: `roofline` (dominant kernel, HBM
-bound, algorithmic bytes / live HIP-event kernel time) and `cpu_baseline` (the
-oracle's C restatement of rowblk.Iter timed on this host's cores on a bounded
-sample; reported, not the target).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps
+and prints the headline figure (`value`, `ms_per_step`) with the workload's
+description.  `--dump-outputs DIR` also writes what the last timed step left in
+the output arrays as DIR/<name>.npy (see dump_outputs).  `--full` adds the
+extra objects, each a measurement or a check of its own: `roofline` (dominant
+kernel, HBM bound, algorithmic bytes / live HIP-event kernel time; the whole
+output copied back and its totals checked), `cpu_baseline` (the oracle's
+C restatement of rowblk.Iter timed on this host's cores on a bounded sample;
+reported, not the target) and `e2e_pcie` (the PCIe-inclusive pipeline).
 """
 from __future__ import annotations
 
@@ -72,12 +77,19 @@ def parse():
     p.add_argument("--zipf-format", choices=["row", "col"], default="row",
                    help="config 5 block format (col = colblk DefaultKeySchema)")
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--full", action="store_true",
+                   help="also the roofline object (whole output copied back and checked), the CPU baseline and the "
+                        "PCIe-inclusive pass; a plain run only times the steps")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the output arrays of the last step as DIR/<name>.npy "
+                        "(float32 / float64; a fixed seeded sample of the long ones)")
     p.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="CPU-baseline threads (0 = the CPUs this process may run on, capped at the box's CPU "
                         "share OMP_NUM_THREADS when that is set)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-e2e", action="store_true", help="skip the host->device->host (PCIe-inclusive) pass")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--no-e2e", action="store_true",
+                   help="--full without the host->device->host (PCIe-inclusive) pass")
     p.add_argument("--e2e-chunk", type=int, default=2048, help="blocks per PCIe pipeline chunk")
     p.add_argument("--kernel", choices=["auto", "single", "pipe", "pool"], default="auto",
                    help="A/B: colblk batches single / pipe "
@@ -216,6 +228,9 @@ def plumbing(a, world, rank, dist) -> None:
         ok = all(torch.equal(firsts.view(world, 4)[r], tot[:r].sum(0)) for r in range(world))
     else:
         ok = True
+    if a.dump_outputs and rank == 0:  # (no decode here: the rebased per-block bases are the step's output)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "blk_bases.npy"), bases.numpy().astype(np.float64))
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": None, "unit": "GiB/s", "n_gpus": world, "steps": a.steps,
                           "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4),
@@ -347,6 +362,95 @@ def global_shard(a, world, rank, dist, dev, nb, N):
     return g, (s, e, world * nb), [int(x) for x in rank_bytes]
 
 
+DUMP_SAMPLE = 1 << 18  # elements kept of a longer array: a dump stays under 64 MB whatever the batch
+
+
+def _dump_array(dirname: str, name: str, x: np.ndarray) -> int:
+    """DIR/<name>.npy, exact in a float type: 8-bit values as float32, 32-bit
+    ones as float64, 64-bit ones as float64 halves <name>_lo32 / <name>_hi32."""
+    if x.dtype.itemsize == 8:
+        u = x.view(np.uint64)
+        return (_dump_array(dirname, name + "_lo32", (u & np.uint64(0xFFFFFFFF)).astype(np.uint32))
+                + _dump_array(dirname, name + "_hi32", (u >> np.uint64(32)).astype(np.uint32)))
+    f = x.astype(np.float32 if x.dtype.itemsize == 1 else np.float64)
+    np.save(os.path.join(dirname, name + ".npy"), f)
+    return f.nbytes
+
+
+def sample_positions(k: int) -> np.ndarray:
+    """The sorted positions a dump keeps of an array of k > DUMP_SAMPLE elements."""
+    return np.sort(np.random.default_rng(20240607).integers(0, k, DUMP_SAMPLE))
+
+
+def dump_outputs(out, dirname: str) -> None:
+    """--dump-outputs: the arrays a caller of the timed path receives (the
+    DecodedBatch that decode_into / TransformPlan.launch filled in the last
+    timed step), each cut to the length its totals give, as DIR/<name>.npy.
+    An array longer than DUMP_SAMPLE is written as its elements at
+    sample_positions(length) (gathered on the device): positions drawn by a
+    fixed-seed generator from the length alone, so two builds that decode the
+    same batch write the same positions."""
+    os.makedirs(dirname, exist_ok=True)
+    t = out.read_totals()
+    nb, n = out.n_blocks, int(t.n_kv)
+    arrays = [("trailer", out.trailer, n), ("kv_flags", out.kv_flags, n), ("entry_off", out.entry_off, n),
+              ("key_off", out.key_off, n + nb), ("val_off", out.val_off, n + nb),
+              ("key_bytes", out.key_bytes, int(t.key_bytes)), ("val_bytes", out.val_bytes, int(t.val_bytes)),
+              ("restarts", out.restarts, int(t.n_restarts)),
+              ("blk_kv_base", out.blk_kv_base, nb + 1), ("blk_key_base", out.blk_key_base, nb + 1),
+              ("blk_val_base", out.blk_val_base, nb + 1), ("blk_rst_base", out.blk_rst_base, nb + 1),
+              ("blk_status", out.blk_status, nb),
+              ("tiering_span_id", out.tiering_span_id, n), ("tiering_attr", out.tiering_attr, n)]
+    total = _dump_array(dirname, "totals", np.array(
+        [t.n_kv, t.key_bytes, t.val_bytes, t.n_restarts, t.status_mask, t.n_bad_blocks], np.uint64))
+    for name, x, k in arrays:
+        if x is None:
+            continue
+        x = x[:k]
+        if k > DUMP_SAMPLE:
+            x = x[torch.from_numpy(sample_positions(k)).to(x.device)]
+        total += _dump_array(dirname, name, x.cpu().numpy())
+    assert total <= 64_000_000, total
+
+
+def roofline(a, kernel, nb, input_bytes, kern_ms, hres, h_in=None) -> dict:
+    """The `roofline` object of a --full line: algorithmic bytes of one launch
+    (from the decoded arrays `hres`; `h_in`: the transform pass's input) over the
+    HIP-event kernel time, and the measured HBM traffic where profiles/ holds
+    it for this workload, kernel and build of the library."""
+    ab = alg_bytes(hres, nb, input_bytes)
+    if h_in is not None:  # the decoded arrays read once, the transformed ones written once
+        ab = alg_bytes(h_in, nb, 0) + alg_bytes(hres, nb, 0) - 24 * nb
+    achieved = ab / (kern_ms * 1e-3) / 1e9
+    traffic = None
+    tname = ("pmc_traffic" if a.workload == "row" and a.kernel == "auto" else
+             f"pmc_traffic_{a.kernel}" if a.workload == "row" else
+             f"pmc_traffic_zipf_ri{a.restart_interval}" if a.workload == "zipf" and a.zipf_format == "row" else
+             f"pmc_traffic_{a.workload}") + (f"_hide{a.hide}" if a.hide else "") + (
+             f"_tier{a.tiering}" if a.tiering else "") + ".json"
+    tp = os.path.join(ROOT, "profiles", tname)
+    if os.path.exists(tp):
+        try:
+            with open(tp) as f:
+                pt = json.load(f)
+            same_zipf = a.workload != "zipf" or (pt.get("restart_interval") == a.restart_interval
+                                                  and pt.get("zipf_format") == a.zipf_format)
+            # the PMC of THIS decode's kernels only (a file names the kernel(s) it measured)
+            # ... and of THIS build of the library (the file records the sha256 of
+            # the .so it was measured on)
+            if (pt.get("workload_blocks") == nb and pt.get("block_size") == a.block_size
+                    and pt.get("workload", "row") == a.workload and same_zipf and pt.get("kernel") == kernel
+                    and pt.get("lib_sha16") == lib_sha16()):
+                traffic = pt.get("hbm_bytes_per_launch")
+        except Exception:
+            traffic = None
+    return {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic, "alg_bytes_per_launch": ab, "kernel_ms": round(kern_ms, 4),
+            "lib_sha16": lib_sha16(), "traffic_source": f"profiles/{tname}" if traffic else None,
+            "input_GiB_per_s_kernel": round(input_bytes / (kern_ms * 1e-3) / 2**30, 1)}
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -407,12 +511,12 @@ def main():
 
     # size the outputs exactly with one decode, then reuse them every step
     first = decode(batch, meta=meta)
-    h = first.to_host()
+    t = first.read_totals()
     if a.hide:  # the visible KVs only: fewer than were written
-        assert 0 < h["n_kv"] < n_kv and h["status_mask"] == 0, (h["n_kv"], n_kv, h["status_mask"])
-        n_kv = h["n_kv"]
-    assert h["n_kv"] == n_kv and h["status_mask"] == 0, (h["n_kv"], n_kv, h["status_mask"])
-    cap = Capacity(kv=h["n_kv"], key=h["key_bytes_total"], val=h["val_bytes_total"], rst=h["n_restarts"])
+        assert 0 < t.n_kv < n_kv and t.status_mask == 0, (t.n_kv, n_kv, t.status_mask)
+        n_kv = int(t.n_kv)
+    assert t.n_kv == n_kv and t.status_mask == 0, (t.n_kv, n_kv, t.status_mask)
+    cap = Capacity(kv=int(t.n_kv), key=int(t.key_bytes), val=int(t.val_bytes), rst=int(t.n_restarts))
     stream = torch.cuda.current_stream(dev)
     plan = None
     if a.workload == "transform":
@@ -421,11 +525,11 @@ def main():
         plan = TransformPlan(first, Transforms(synthetic_seq_num=12345, hide_obsolete_points=True,
                                                synthetic_prefix=b"tenant-0042/"), stream)
         out = plan.out
-        h_in = h
+        h_in = first.to_host() if a.full else None  # (the roofline's bytes read)
     else:
         del first
+        h_in = None
         out = DecodedBatch.allocate(nb, cap, dev, meta=meta)
-    del h
     gathered = torch.zeros(world * 4, dtype=torch.int64, device=dev) if world > 1 else None
     if world > 1 and a.dist_backend == "gloo":  # (gloo gathers host tensors)
         gathered = gathered.cpu()
@@ -452,8 +556,9 @@ def main():
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize(dev)
-    hres = out.to_host()
-    assert hres["n_kv"] == n_kv and hres["status_mask"] == 0
+    if a.warmup:
+        t = out.read_totals()
+        assert t.n_kv == n_kv and t.status_mask == 0, (t.n_kv, n_kv, t.status_mask)
 
     # kernel-only timing with HIP events on the launch stream
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
@@ -471,44 +576,13 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
-    kern_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        km = torch.tensor([kern_ms], dtype=torch.float64, device=dev)
-        dist.all_reduce(km, op=dist.ReduceOp.MAX)
-        kern_ms = float(km.item())
 
     total_input = int(sum(rank_bytes))
     value = total_input * a.steps / elapsed / 2**30
-    ab = alg_bytes(hres, nb, input_bytes)
-    if plan is not None:  # the decoded arrays read once, the transformed ones written once
-        ab = alg_bytes(h_in, nb, 0) + alg_bytes(hres, nb, 0) - 24 * nb
-    achieved = ab / (kern_ms * 1e-3) / 1e9
-    traffic = None
-    tname = ("pmc_traffic" if a.workload == "row" and a.kernel == "auto" else
-             f"pmc_traffic_{a.kernel}" if a.workload == "row" else
-             f"pmc_traffic_zipf_ri{a.restart_interval}" if a.workload == "zipf" and a.zipf_format == "row" else
-             f"pmc_traffic_{a.workload}") + (f"_hide{a.hide}" if a.hide else "") + (
-             f"_tier{a.tiering}" if a.tiering else "") + ".json"
-    tp = os.path.join(ROOT, "profiles", tname)
-    if os.path.exists(tp):
-        try:
-            with open(tp) as f:
-                pt = json.load(f)
-            same_zipf = a.workload != "zipf" or (pt.get("restart_interval") == a.restart_interval
-                                                  and pt.get("zipf_format") == a.zipf_format)
-            # the PMC of THIS decode's kernels only (a file names the kernel(s) it measured)
-            # ... and of THIS build of the library (the file records the sha256 of
-            # the .so it was measured on)
-            if (pt.get("workload_blocks") == nb and pt.get("block_size") == a.block_size
-                    and pt.get("workload", "row") == a.workload and same_zipf and pt.get("kernel") == kernel
-                    and pt.get("lib_sha16") == lib_sha16()):
-                traffic = pt.get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
-
     res = {
         "metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True,
@@ -519,17 +593,25 @@ def main():
                    "input_bytes_per_rank": [int(x) for x in rank_bytes],
                    "parallelism": f"shard{world}" + (f"+{'rccl' if a.dist_backend == 'nccl' else 'gloo'}_offset_concat"
                                                       if world > 1 else "")},
-        "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": traffic, "alg_bytes_per_launch": ab, "kernel_ms": round(kern_ms, 4),
-                     "lib_sha16": lib_sha16(), "traffic_source": f"profiles/{tname}" if traffic else None,
-                     "input_GiB_per_s_kernel": round(input_bytes / (kern_ms * 1e-3) / 2**30, 1)},
     }
 
-    if rank == 0 and not a.no_cpu_baseline and plan is None:
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
+
+    if a.full:
+        kern_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
+        if world > 1:
+            km = torch.tensor([kern_ms], dtype=torch.float64, device=dev)
+            dist.all_reduce(km, op=dist.ReduceOp.MAX)
+            kern_ms = float(km.item())
+        hres = out.to_host()  # the whole output, checked against the generator's count
+        assert hres["n_kv"] == n_kv and hres["status_mask"] == 0
+        res["roofline"] = roofline(a, kernel, nb, input_bytes, kern_ms, hres, h_in)
+
+    if a.full and rank == 0 and not a.no_cpu_baseline and plan is None:
         res["cpu_baseline"] = cpu_baseline(a, buf, off, lens, fmt, block_fmt, flags & 0xFF)
 
-    if not a.no_e2e and rank == 0 and plan is None:
+    if a.full and not a.no_e2e and rank == 0 and plan is None:
         del out  # (HBM for the pipeline's slots)
         torch.cuda.empty_cache()
         res["e2e_pcie"] = e2e_rate(buf, off, lens, flags & ~(N.PBL_BATCH_VARLEN | N.PBL_COL_TIERING), dev, cap, fmt,

@@ -14,7 +14,7 @@ fi
 if [ -n "${SMOKE:-}" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && tail -2 $O/smoke.log || exit 1
 fi
-B="timeout -k 10 200 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-e2e"
+B="timeout -k 10 200 python bench.py --steps ${STEPS:-10} --warmup 2 --full --no-cpu-baseline --no-e2e"
 run() { n=$1; shift; $B "$@" > $O/bench_$n.json 2>$O/bench_$n.err || { tail -5 $O/bench_$n.err; exit 1; }; python -c "import json; d=json.load(open('$O/bench_$n.json')); print('$n', round(d['value'],1), d['roofline']['kernel_ms'], d['roofline']['frac'], d['roofline'].get('traffic'))"; }
 for w in ${BENCH:-row col}; do
   case $w in
