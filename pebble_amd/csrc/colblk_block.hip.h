@@ -24,6 +24,8 @@
 //     global -> global with aligned 16-B loads and a funnel shift, never staged.
 #pragma once
 
+#include "common.hip.h"
+
 namespace pbl {
 namespace col {
 
@@ -462,7 +464,42 @@ __device__ __forceinline__ uint32_t lds_copy(lds_u8 kb, uint32_t dst, lds_cu8 sr
 #define PBL_COL_KEYCOPY16 1  // staged keys: segment copies 16 B at a time (else byte by byte)
 #endif
 
-// MaterializeUserKey of row r into LDS bytes kb[dst ..).
+// A crdb1 key's MVCC timestamp suffix at out[n ..): wall (8 B big-endian), the
+// logical part (4 B) if it has one, and the suffix's length byte.
+template <class Out>
+__device__ __forceinline__ void put_mvcc(Out out, uint32_t n, const RowParts& p) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) out[n++] = uint8_t(p.wall >> (56 - 8 * i));
+  if (p.logical != 0) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) out[n++] = uint8_t(p.logical >> (24 - 8 * i));
+  }
+  out[n] = p.logical != 0 ? 13 : 9;
+}
+
+// MaterializeUserKey of row r, byte by byte to out[0 ..) (LDS or global memory).
+template <bool F, class Out>
+__device__ __forceinline__ void key_bytes(const Src& S, const Desc& d, uint32_t schema, const RowParts& p, Out out) {
+  uint32_t n = 0;
+  for (uint32_t i = 0; i < d.shared_len; i++) out[n++] = uint8_t(key_byte<F>(S, d.pb_data + i));
+  for (uint32_t o = p.bl; o < p.bh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
+  for (uint32_t o = p.sl; o < p.sh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
+  if (schema == PBL_FMT_COL_CRDB1) {
+    out[n++] = 0;
+    if (p.wall == 0 && p.logical == 0) {
+      if (p.uh > p.ul) {
+        for (uint32_t o = p.ul; o < p.uh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
+        out[n++] = uint8_t(p.uh - p.ul + 1);
+      }
+    } else {
+      put_mvcc(out, n, p);
+    }
+  } else {
+    for (uint32_t o = p.ul; o < p.uh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
+  }
+}
+
+// The same key into LDS bytes kb[dst ..).
 template <bool F>
 __device__ __forceinline__ void build_key(const Src& S, const Desc& d, uint32_t schema, const RowParts& p,
                                           lds_u8 kb, uint32_t dst) {
@@ -479,74 +516,14 @@ __device__ __forceinline__ void build_key(const Src& S, const Desc& d, uint32_t 
           kb[dst++] = uint8_t(p.uh - p.ul + 1);
         }
       } else {
-#pragma unroll
-        for (int i = 0; i < 8; i++) kb[dst++] = uint8_t(p.wall >> (56 - 8 * i));
-        if (p.logical == 0) {
-          kb[dst++] = 9;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; i++) kb[dst++] = uint8_t(p.logical >> (24 - 8 * i));
-          kb[dst++] = 13;
-        }
+        put_mvcc(kb, dst, p);
       }
     } else {
       lds_copy(kb, dst, H + p.ul, p.uh - p.ul);
     }
     return;
   }
-  for (uint32_t i = 0; i < d.shared_len; i++) kb[dst++] = uint8_t(key_byte<F>(S, d.pb_data + i));
-  for (uint32_t o = p.bl; o < p.bh; o++) kb[dst++] = uint8_t(key_byte<F>(S, o));
-  for (uint32_t o = p.sl; o < p.sh; o++) kb[dst++] = uint8_t(key_byte<F>(S, o));
-  if (schema == PBL_FMT_COL_CRDB1) {
-    kb[dst++] = 0;
-    if (p.wall == 0 && p.logical == 0) {
-      if (p.uh > p.ul) {
-        for (uint32_t o = p.ul; o < p.uh; o++) kb[dst++] = uint8_t(key_byte<F>(S, o));
-        kb[dst++] = uint8_t(p.uh - p.ul + 1);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; i++) kb[dst++] = uint8_t(p.wall >> (56 - 8 * i));
-      if (p.logical == 0) {
-        kb[dst++] = 9;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; i++) kb[dst++] = uint8_t(p.logical >> (24 - 8 * i));
-        kb[dst++] = 13;
-      }
-    }
-  } else {
-    for (uint32_t o = p.ul; o < p.uh; o++) kb[dst++] = uint8_t(key_byte<F>(S, o));
-  }
-}
-
-// Same key, straight to global memory (chunks whose keys exceed the LDS buffer).
-template <bool F>
-__device__ __forceinline__ void build_key_global(const Src& S, const Desc& d, uint32_t schema, const RowParts& p,
-                                                 uint8_t* out) {
-  uint32_t n = 0;
-  for (uint32_t i = 0; i < d.shared_len; i++) out[n++] = uint8_t(key_byte<F>(S, d.pb_data + i));
-  for (uint32_t o = p.bl; o < p.bh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
-  for (uint32_t o = p.sl; o < p.sh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
-  if (schema == PBL_FMT_COL_CRDB1) {
-    out[n++] = 0;
-    if (p.wall == 0 && p.logical == 0) {
-      if (p.uh > p.ul) {
-        for (uint32_t o = p.ul; o < p.uh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
-        out[n++] = uint8_t(p.uh - p.ul + 1);
-      }
-    } else {
-      for (int i = 0; i < 8; i++) out[n++] = uint8_t(p.wall >> (56 - 8 * i));
-      if (p.logical == 0) {
-        out[n++] = 9;
-      } else {
-        for (int i = 0; i < 4; i++) out[n++] = uint8_t(p.logical >> (24 - 8 * i));
-        out[n++] = 13;
-      }
-    }
-  } else {
-    for (uint32_t o = p.ul; o < p.uh; o++) out[n++] = uint8_t(key_byte<F>(S, o));
-  }
+  key_bytes<F>(S, d, schema, p, kb + dst);
 }
 
 // bytes [a, a+16) of an LDS word array (a may be unaligned)
@@ -555,20 +532,6 @@ __device__ __forceinline__ uint4 lds_bytes16(lds_cu32 W, uint32_t a) {
   const uint32_t w0 = W[k], w1 = W[k + 1], w2 = W[k + 2], w3 = W[k + 3], w4 = W[k + 4];
   return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, s), __builtin_amdgcn_alignbyte(w2, w1, s),
                     __builtin_amdgcn_alignbyte(w3, w2, s), __builtin_amdgcn_alignbyte(w4, w3, s));
-}
-
-// 16 bytes starting `sh` bytes into the 32-byte pair (x, y)
-__device__ __forceinline__ uint4 funnel16(const uint4& x, const uint4& y, uint32_t sh) {
-  const uint32_t s = sh & 3;
-  uint32_t d0, d1, d2, d3, d4;
-  switch (sh >> 2) {
-    case 0: d0 = x.x; d1 = x.y; d2 = x.z; d3 = x.w; d4 = y.x; break;
-    case 1: d0 = x.y; d1 = x.z; d2 = x.w; d3 = y.x; d4 = y.y; break;
-    case 2: d0 = x.z; d1 = x.w; d2 = y.x; d3 = y.y; d4 = y.z; break;
-    default: d0 = x.w; d1 = y.x; d2 = y.y; d3 = y.z; d4 = y.w; break;
-  }
-  return make_uint4(__builtin_amdgcn_alignbyte(d1, d0, s), __builtin_amdgcn_alignbyte(d2, d1, s),
-                    __builtin_amdgcn_alignbyte(d3, d2, s), __builtin_amdgcn_alignbyte(d4, d3, s));
 }
 
 // Stage block bytes [lo, lo + n) (lo a multiple of 16) into LDS granules.
@@ -585,6 +548,69 @@ __device__ __forceinline__ void stage(lds_u4 dst, const uint8_t* blocks, uint64_
     const uint4 y = ynext < a1 ? G[g + 1] : make_uint4(0, 0, 0, 0);
     const uint4 z = funnel16(x, y, ph);
     dst[g] = u32x4{z.x, z.y, z.z, z.w};
+  }
+}
+
+// ---- per-row rules shared by every colblk emit (DataBlockIter, data_block.go) ---
+// Bit r of the bitmap column at block offset `at` (0: the block has none).
+__device__ __forceinline__ bool row_bit(const Src& S, uint32_t at, uint32_t r) {
+  return at && ((S.le(at + 8 * (r >> 6), 8) >> (r & 63)) & 1);
+}
+// Row r's isObsolete bit (data_block.go:519; HideObsoletePoints skips such
+// rows, :1680-1697) and the values column's offset r.
+__device__ __forceinline__ bool row_obsolete(const Src& S, const Desc& d, uint32_t r) {
+  return row_bit(S, d.obs_at, r);
+}
+__device__ __forceinline__ uint32_t row_voff(const Src& S, const Desc& d, uint32_t r) {
+  return d.v_off.w ? uint32_t(S.le(d.v_off.at + r * d.v_off.w, d.v_off.w)) : 0u;
+}
+// PBL_KV_* flags of row r, whose value is values bytes [v, v1): prefix changed,
+// obsolete, and for a row of the external-value bitmap the handle's kind (the
+// value prefix byte, sstable/block/kv.go:14-41).
+__device__ __forceinline__ uint8_t row_flags(const Src& S, const Desc& d, uint32_t r, uint32_t v, uint32_t v1) {
+  uint8_t fl = 0;
+  if (row_bit(S, d.pc_at, r)) fl |= PBL_KV_PREFIX_CHANGED;
+  if (row_bit(S, d.obs_at, r)) fl |= PBL_KV_OBSOLETE;
+  if (row_bit(S, d.ext_at, r))
+    fl |= (v1 > v && (S.byte(d.v_data + v) & 0xC0) == 0x80) ? PBL_KV_VALBLK_HANDLE : PBL_KV_BLOB_HANDLE;
+  return fl;
+}
+// Row r's trailer with the batch's SyntheticSeqNum (data_block.go:1680-1697).
+template <bool F>
+__device__ __forceinline__ uint64_t row_trailer(const Src& S, const Desc& d, uint32_t r, uint64_t seq) {
+  return with_seq(u_at<F>(S, d.trailers, r), seq, 0u);
+}
+// Row r's KVMeta pair (decodeMeta, data_block.go:1633-1641).
+__device__ __forceinline__ void row_meta(const Src& S, const Desc& d, uint32_t r, uint64_t* span, uint64_t* attr) {
+  *span = u_at_any(S, d.span, r);
+  *attr = u_at_any(S, d.attr, r);
+}
+
+// `tot` key bytes built at kb8 + kKeyPad to out[lo, lo + tot), as aligned
+// 16-B granules over kThreads threads (kWave: one wave; kTPB: the workgroup).
+template <int kThreads>
+__device__ __forceinline__ void keys_out(lds_u8 kb8, uint8_t* out, uint64_t lo, uint32_t tot) {
+  const uint32_t t = kThreads == kWave ? uint32_t(lane_id()) : threadIdx.x;
+  const uint64_t hi = lo + tot;
+  const lds_cu32 W = (lds_cu32)kb8;
+  for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * t; ga < hi; ga += 16ull * kThreads)
+    store16(out, ga, lo, hi, lds_bytes16(W, uint32_t(kKeyPad + ga - lo)));
+}
+// One chunk of keys (a row per thread: parts p at exclusive offset ex of the
+// chunk's `tot` bytes; `live`: the thread has a row) to out[lo, lo + tot):
+// built in the key buffer kb8 (`cap` bytes) and copied out by keys_out, or past
+// the buffer written byte by byte to global memory (no barrier then).  The
+// caller places a barrier before the buffer's next use.
+template <bool F, int kThreads, class Barrier>
+__device__ __forceinline__ void emit_key_chunk(const Src& S, const Desc& d, uint32_t schema, const RowParts& p,
+                                               bool live, uint32_t ex, uint32_t tot, lds_u8 kb8, uint32_t cap,
+                                               uint8_t* out, uint64_t lo, Barrier barrier) {
+  if (tot <= cap) {
+    if (live) build_key<F>(S, d, schema, p, kb8, kKeyPad + ex);
+    barrier();
+    keys_out<kThreads>(kb8, out, lo, tot);
+  } else if (live) {
+    key_bytes<F>(S, d, schema, p, out + lo + ex);
   }
 }
 
@@ -691,27 +717,18 @@ __device__ __forceinline__ void col_rows(Lds& s, const Args& A, uint32_t b, uint
   const uint64_t kvb = s.bases[0], kbb = s.bases[1], vbb = s.bases[2];
 
   // ---- per-row arrays ------------------------------------------------------------
-  const UCol& vo = d.v_off;
   for (uint32_t r = t; r <= rows; r += kTPB) {
-    const uint32_t v = vo.w ? uint32_t(S.le(vo.at + r * vo.w, vo.w)) : 0;
+    const uint32_t v = row_voff(S, d, r);
     O.val_off[kvb + b + r] = v - d.v_lo;
     if (r < rows) {
-      O.trailer[kvb + r] = with_seq(u_at<F>(S, d.trailers, r), A.in.synthetic_seq_num, 0u);
-      if (O.kv_flags) {
-        uint8_t fl = 0;
-        if (d.pc_at && ((S.le(d.pc_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) fl |= PBL_KV_PREFIX_CHANGED;
-        if (d.obs_at && ((S.le(d.obs_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) fl |= PBL_KV_OBSOLETE;
-        if (d.ext_at && ((S.le(d.ext_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) {
-          const uint32_t v1 = vo.w ? uint32_t(S.le(vo.at + (r + 1) * vo.w, vo.w)) : 0;
-          const bool vb = v1 > v && (S.byte(d.v_data + v) & 0xC0) == 0x80;
-          fl |= vb ? PBL_KV_VALBLK_HANDLE : PBL_KV_BLOB_HANDLE;
-        }
-        O.kv_flags[kvb + r] = fl;
-      }
+      O.trailer[kvb + r] = row_trailer<F>(S, d, r, A.in.synthetic_seq_num);
+      if (O.kv_flags) O.kv_flags[kvb + r] = row_flags(S, d, r, v, row_voff(S, d, r + 1));
       if (O.entry_off) O.entry_off[kvb + r] = r;
-      if (O.tiering_span_id) {  // decodeMeta (data_block.go:1633-1641)
-        O.tiering_span_id[kvb + r] = u_at_any(S, d.span, r);
-        O.tiering_attr[kvb + r] = u_at_any(S, d.attr, r);
+      if (O.tiering_span_id) {
+        uint64_t span, attr;
+        row_meta(S, d, r, &span, &attr);
+        O.tiering_span_id[kvb + r] = span;
+        O.tiering_attr[kvb + r] = attr;
       }
     }
   }
@@ -720,10 +737,7 @@ __device__ __forceinline__ void col_rows(Lds& s, const Args& A, uint32_t b, uint
   if (prebuilt) {
     if (uint32_t(t) < rows) O.key_off[kvb + b + t] = excl0;
     if (t == 0) O.key_off[kvb + b + rows] = tot0;
-    const uint64_t lo = kbb, hi = kbb + tot0;
-    const lds_cu32 W = (lds_cu32)to_lds(s.key4);
-    for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * t; ga < hi; ga += 16ull * kTPB)
-      store16(O.key_bytes, ga, lo, hi, lds_bytes16(W, uint32_t(kKeyPad + ga - lo)));
+    keys_out<kTPB>(kb8, O.key_bytes, kbb, tot0);
   } else {
     uint32_t cbase = 0;
     for (uint32_t c = 0; c < nch; c++) {
@@ -734,16 +748,8 @@ __device__ __forceinline__ void col_rows(Lds& s, const Args& A, uint32_t b, uint
       uint32_t ex, tot, de, dt;
       block_excl_scan2(p.klen, 0u, &ex, &de, s.scratch, &tot, &dt);
       if (r < rows) O.key_off[kvb + b + r] = cbase + ex;
-      if (tot <= kKeyBuf) {
-        if (r < rows) build_key<F>(S, d, schema, p, kb8, kKeyPad + ex);
-        __syncthreads();
-        const uint64_t lo = kbb + cbase, hi = lo + tot;
-        const lds_cu32 W = (lds_cu32)to_lds(s.key4);
-        for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * t; ga < hi; ga += 16ull * kTPB)
-          store16(O.key_bytes, ga, lo, hi, lds_bytes16(W, uint32_t(kKeyPad + ga - lo)));
-      } else if (r < rows) {
-        build_key_global<F>(S, d, schema, p, O.key_bytes + kbb + cbase + ex);
-      }
+      emit_key_chunk<F, kTPB>(S, d, schema, p, r < rows, ex, tot, kb8, kKeyBuf, O.key_bytes, kbb + cbase,
+                              [] { __syncthreads(); });
       cbase += tot;
       __syncthreads();
     }
@@ -774,15 +780,6 @@ __device__ __forceinline__ void col_rows(Lds& s, const Args& A, uint32_t b, uint
       store16(O.val_bytes, ga, lo, hi, sh ? funnel16(x, y, sh) : x);
     }
   }
-}
-
-// Row r's isObsolete bit (data_block.go:519; HideObsoletePoints skips such
-// rows, :1680-1697) and the values column's offset r.
-__device__ __forceinline__ bool row_obsolete(const Src& S, const Desc& d, uint32_t r) {
-  return d.obs_at && ((S.le(d.obs_at + 8 * (r >> 6), 8) >> (r & 63)) & 1);
-}
-__device__ __forceinline__ uint32_t row_voff(const Src& S, const Desc& d, uint32_t r) {
-  return d.v_off.w ? uint32_t(S.le(d.v_off.at + r * d.v_off.w, d.v_off.w)) : 0u;
 }
 
 }  // namespace col

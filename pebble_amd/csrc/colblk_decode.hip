@@ -66,15 +66,15 @@ extern "C" int pbl_decode_batch_colblk(const pbl_block_batch* batch, pbl_decode_
       hipLaunchKernelGGL((cw::colblk_wave_emit_kernel<PBL_CW_STAGE, false>), dim3(batch->n_blocks), dim3(pbl::kWave),
                          0, st, a, no_ids);
   } else {
-    const void* fn = hide ? reinterpret_cast<const void*>(pbl::col::cpipe::colblk_pipe_kernel<true>)
-                          : reinterpret_cast<const void*>(pbl::col::cpipe::colblk_pipe_kernel<false>);
+    namespace cp = pbl::col::cpipe;
+    const void* fn = pbl::with_bool(
+        hide, [](auto h) { return reinterpret_cast<const void*>(cp::colblk_pipe_kernel<decltype(h)::value>); });
     const uint64_t grid = pbl::persistent_grid(st, hide ? pbl::kKColPipeHide : pbl::kKColPipe, fn, batch->n_blocks,
                                                nullptr);
     if (!grid) return PBL_DEVICE_ERROR;
-    if (hide)
-      hipLaunchKernelGGL(pbl::col::cpipe::colblk_pipe_kernel<true>, dim3(uint32_t(grid)), dim3(pbl::kTPB), 0, st, a);
-    else
-      hipLaunchKernelGGL(pbl::col::cpipe::colblk_pipe_kernel<false>, dim3(uint32_t(grid)), dim3(pbl::kTPB), 0, st, a);
+    pbl::with_bool(hide, [&](auto h) {
+      hipLaunchKernelGGL(cp::colblk_pipe_kernel<decltype(h)::value>, dim3(uint32_t(grid)), dim3(pbl::kTPB), 0, st, a);
+    });
   }
   return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
 }

@@ -300,23 +300,12 @@ __device__ __forceinline__ void col_emit_rows(CLds& L, const Slot& E, const Args
   const gptr<uint32_t> entry_off = to_glb(O.entry_off);
 
   // per-row arrays
-  const UCol& vo = d.v_off;
   for (uint32_t r = t; r <= rows; r += kTPB) {
-    const uint32_t v = vo.w ? uint32_t(S.le(vo.at + r * vo.w, vo.w)) : 0;
+    const uint32_t v = row_voff(S, d, r);
     val_off[kvb + b + r] = v - d.v_lo;
     if (r < rows) {
-      trailer[kvb + r] = with_seq(u_at<F>(S, d.trailers, r), A.in.synthetic_seq_num, 0u);
-      if (O.kv_flags) {
-        uint8_t fl = 0;
-        if (d.pc_at && ((S.le(d.pc_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) fl |= PBL_KV_PREFIX_CHANGED;
-        if (d.obs_at && ((S.le(d.obs_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) fl |= PBL_KV_OBSOLETE;
-        if (d.ext_at && ((S.le(d.ext_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) {
-          const uint32_t v1 = vo.w ? uint32_t(S.le(vo.at + (r + 1) * vo.w, vo.w)) : 0;
-          const bool vb = v1 > v && (S.byte(d.v_data + v) & 0xC0) == 0x80;
-          fl |= vb ? PBL_KV_VALBLK_HANDLE : PBL_KV_BLOB_HANDLE;
-        }
-        kv_flags[kvb + r] = fl;
-      }
+      trailer[kvb + r] = row_trailer<F>(S, d, r, A.in.synthetic_seq_num);
+      if (O.kv_flags) kv_flags[kvb + r] = row_flags(S, d, r, v, row_voff(S, d, r + 1));
       if (O.entry_off) entry_off[kvb + r] = r;
     }
   }
@@ -329,10 +318,7 @@ __device__ __forceinline__ void col_emit_rows(CLds& L, const Slot& E, const Args
   if (prebuilt) {
     // single chunk, built in LDS while wave 0 resolved the look-back
     if (uint32_t(t) < rows) key_off[kvb + b + t] = ex0;
-    const uint64_t lo = kbb, hi = kbb + tot0;
-    const lds_cu32 W = (lds_cu32)to_lds(L.key4);
-    for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * t; ga < hi; ga += 16ull * kTPB)
-      store16(O.key_bytes, ga, lo, hi, lds_bytes16(W, uint32_t(kKeyPad + ga - lo)));
+    keys_out<kTPB>(kb8, O.key_bytes, kbb, tot0);
     cbase = tot0;
   }
   for (uint32_t c = 0; c < (prebuilt ? 0u : nch); c++) {
@@ -346,12 +332,9 @@ __device__ __forceinline__ void col_emit_rows(CLds& L, const Slot& E, const Args
     if (tot <= kKeyBuf) {
       if (r < rows) build_key<F>(S, d, schema, p, kb8, kKeyPad + ex);
       __syncthreads();
-      const uint64_t lo = kbb + cbase, hi = lo + tot;
-      const lds_cu32 W = (lds_cu32)to_lds(L.key4);
-      for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * t; ga < hi; ga += 16ull * kTPB)
-        store16(O.key_bytes, ga, lo, hi, lds_bytes16(W, uint32_t(kKeyPad + ga - lo)));
+      keys_out<kTPB>(kb8, O.key_bytes, kbb + cbase, tot);
     } else if (r < rows) {
-      build_key_global<F>(S, d, schema, p, O.key_bytes + kbb + cbase + ex);
+      key_bytes<F>(S, d, schema, p, O.key_bytes + kbb + cbase + ex);
     }
     cbase += tot;
     __syncthreads();
@@ -386,8 +369,10 @@ __device__ __forceinline__ void col_emit_rows(CLds& L, const Slot& E, const Args
   // copies, so the per-row loop above keeps its register budget
   if (O.tiering_span_id) {
     for (uint32_t r = t; r < rows; r += kTPB) {
-      to_glb(O.tiering_span_id)[kvb + r] = u_at_any(S, d.span, r);
-      to_glb(O.tiering_attr)[kvb + r] = u_at_any(S, d.attr, r);
+      uint64_t span, attr;
+      row_meta(S, d, r, &span, &attr);
+      to_glb(O.tiering_span_id)[kvb + r] = span;
+      to_glb(O.tiering_attr)[kvb + r] = attr;
     }
   }
   CSTAMP(A, b, 7);
@@ -432,33 +417,17 @@ __device__ __forceinline__ void col_emit_rows_hide(CLds& L, const Slot& E, const
       const uint64_t i = kvb + cn + en;
       to_glb(O.key_off)[i + b] = ck + ek;
       to_glb(O.val_off)[i + b] = cv + ev;
-      to_glb(O.trailer)[i] = with_seq(u_at<F>(S, d.trailers, r), A.in.synthetic_seq_num, 0u);
-      if (O.kv_flags) {
-        uint8_t fl = 0;
-        if (d.pc_at && ((S.le(d.pc_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) fl |= PBL_KV_PREFIX_CHANGED;
-        if (d.ext_at && ((S.le(d.ext_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) {
-          const bool vb = v1 > v0 && (S.byte(d.v_data + v0) & 0xC0) == 0x80;
-          fl |= vb ? PBL_KV_VALBLK_HANDLE : PBL_KV_BLOB_HANDLE;
-        }
-        to_glb(O.kv_flags)[i] = fl;
-      }
+      to_glb(O.trailer)[i] = row_trailer<F>(S, d, r, A.in.synthetic_seq_num);
+      if (O.kv_flags) to_glb(O.kv_flags)[i] = row_flags(S, d, r, v0, v1);  // (a visible row: never OBSOLETE)
       if (O.entry_off) to_glb(O.entry_off)[i] = r;
       L.rv0[en] = d.v_data + v0;
       L.rvo[en] = ev;
       L.rvl[en] = v1 - v0;
     }
     // keys
-    if (tk <= kKeyBuf) {
-      if (vis) build_key<F>(S, d, schema, p, kb8, kKeyPad + ek);
-      __syncthreads();
-      const uint64_t lo = kbb + ck, hi = lo + tk;
-      const lds_cu32 W = (lds_cu32)to_lds(L.key4);
-      for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * t; ga < hi; ga += 16ull * kTPB)
-        store16(O.key_bytes, ga, lo, hi, lds_bytes16(W, uint32_t(kKeyPad + ga - lo)));
-    } else {
-      if (vis) build_key_global<F>(S, d, schema, p, O.key_bytes + kbb + ck + ek);
-      __syncthreads();
-    }
+    emit_key_chunk<F, kTPB>(S, d, schema, p, vis, ek, tk, kb8, kKeyBuf, O.key_bytes, kbb + ck,
+                            [] { __syncthreads(); });
+    if (tk > kKeyBuf) __syncthreads();  // (the row arrays, which the key build's barrier orders otherwise)
     // values: 8 threads per visible row
     const gptr<uint8_t> vout = to_glb(O.val_bytes) + vbb + cv;
     const uint32_t q8 = uint32_t(t) & 7u;
@@ -474,9 +443,11 @@ __device__ __forceinline__ void col_emit_rows_hide(CLds& L, const Slot& E, const
         for (uint32_t o = q8; o < len; o += 8) vout[o0 + o] = uint8_t(S.byte(src + o));
       }
     }
-    if (O.tiering_span_id && vis) {  // KVMeta (decodeMeta, data_block.go:1633-1641)
-      to_glb(O.tiering_span_id)[kvb + cn + en] = u_at_any(S, d.span, r);
-      to_glb(O.tiering_attr)[kvb + cn + en] = u_at_any(S, d.attr, r);
+    if (O.tiering_span_id && vis) {
+      uint64_t span, attr;
+      row_meta(S, d, r, &span, &attr);
+      to_glb(O.tiering_span_id)[kvb + cn + en] = span;
+      to_glb(O.tiering_attr)[kvb + cn + en] = attr;
     }
     cn += tn;
     ck += tk;

@@ -171,27 +171,18 @@ __device__ __forceinline__ void cw_emit(L_& L, const Args& A, uint32_t b, uint32
   const gptr<const uint8_t> g = to_glb(A.in.blocks + A.in.block_off[b]);
 
   // ---- per-row arrays ----------------------------------------------------------
-  const UCol& vo = d.v_off;
   for (uint32_t r = l; r <= rows; r += kWave) {
-    const uint32_t v = vo.w ? uint32_t(S.le(vo.at + r * vo.w, vo.w)) : 0;
+    const uint32_t v = row_voff(S, d, r);
     st_nt(to_glb(O.val_off) + (kvb + b + r), v - d.v_lo);
     if (r < rows) {
-      st_nt(to_glb(O.trailer) + (kvb + r), with_seq(u_at<F>(S, d.trailers, r), A.in.synthetic_seq_num, 0u));
-      if (O.kv_flags) {
-        uint8_t fl = 0;
-        if (d.pc_at && ((S.le(d.pc_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) fl |= PBL_KV_PREFIX_CHANGED;
-        if (d.obs_at && ((S.le(d.obs_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) fl |= PBL_KV_OBSOLETE;
-        if (d.ext_at && ((S.le(d.ext_at + 8 * (r >> 6), 8) >> (r & 63)) & 1)) {
-          const uint32_t v1 = vo.w ? uint32_t(S.le(vo.at + (r + 1) * vo.w, vo.w)) : 0;
-          const bool vb = v1 > v && (S.byte(d.v_data + v) & 0xC0) == 0x80;
-          fl |= vb ? PBL_KV_VALBLK_HANDLE : PBL_KV_BLOB_HANDLE;
-        }
-        st_nt(to_glb(O.kv_flags) + (kvb + r), fl);
-      }
+      st_nt(to_glb(O.trailer) + (kvb + r), row_trailer<F>(S, d, r, A.in.synthetic_seq_num));
+      if (O.kv_flags) st_nt(to_glb(O.kv_flags) + (kvb + r), row_flags(S, d, r, v, row_voff(S, d, r + 1)));
       if (O.entry_off) st_nt(to_glb(O.entry_off) + (kvb + r), r);
-      if (O.tiering_span_id) {  // decodeMeta (data_block.go:1633-1641)
-        st_nt(to_glb(O.tiering_span_id) + (kvb + r), u_at_any(S, d.span, r));
-        st_nt(to_glb(O.tiering_attr) + (kvb + r), u_at_any(S, d.attr, r));
+      if (O.tiering_span_id) {
+        uint64_t span, attr;
+        row_meta(S, d, r, &span, &attr);
+        st_nt(to_glb(O.tiering_span_id) + (kvb + r), span);
+        st_nt(to_glb(O.tiering_attr) + (kvb + r), attr);
       }
     }
   }
@@ -199,7 +190,6 @@ __device__ __forceinline__ void cw_emit(L_& L, const Args& A, uint32_t b, uint32
 
   // ---- keys: 64 rows at a time, built in the key buffer -------------------------
   lds_u8 kb8 = (lds_u8)to_lds(L.key4);
-  const lds_cu32 KW = (lds_cu32)to_lds(L.key4);
   constexpr uint32_t kKeyCap = uint32_t(sizeof(L.key4)) - 2 * kKeyPad;
   uint32_t cbase = 0;
   for (uint32_t r0 = 0; r0 < rows; r0 += kWave) {
@@ -210,16 +200,9 @@ __device__ __forceinline__ void cw_emit(L_& L, const Args& A, uint32_t b, uint32
     const uint32_t incl = wave_incl_scan(p.klen);
     const uint32_t tot = __shfl(incl, kWave - 1, kWave), ex = incl - p.klen;
     if (r < rows) st_nt(to_glb(O.key_off) + (kvb + b + r), cbase + ex);
-    if (tot <= kKeyCap) {
-      if (r < rows) build_key<F>(S, d, schema, p, kb8, kKeyPad + ex);
-      wave_sync();
-      const uint64_t lo = kbb + cbase, hi = lo + tot;
-      for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * l; ga < hi; ga += 16ull * kWave)
-        store16(O.key_bytes, ga, lo, hi, lds_bytes16(KW, uint32_t(kKeyPad + ga - lo)));
-      wave_sync();  // (the buffer is the next chunk's)
-    } else if (r < rows) {
-      build_key_global<F>(S, d, schema, p, O.key_bytes + kbb + cbase + ex);
-    }
+    emit_key_chunk<F, kWave>(S, d, schema, p, r < rows, ex, tot, kb8, kKeyCap, O.key_bytes, kbb + cbase,
+                             [] { wave_sync(); });
+    wave_sync();  // (the buffer is the next chunk's)
     cbase += tot;
   }
   if (l == 0) st_nt(to_glb(O.key_off) + (kvb + b + rows), cbase);

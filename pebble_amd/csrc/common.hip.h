@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/pebble_amd.h"
 
 namespace pbl {
@@ -446,6 +448,20 @@ struct Args {
   pbl_decode_out out;
 };
 
+// 16 bytes starting `sh` bytes into the 32-byte pair (x, y)
+__device__ __forceinline__ uint4 funnel16(const uint4& x, const uint4& y, uint32_t sh) {
+  const uint32_t s = sh & 3;
+  uint32_t d0, d1, d2, d3, d4;
+  switch (sh >> 2) {
+    case 0: d0 = x.x; d1 = x.y; d2 = x.z; d3 = x.w; d4 = y.x; break;
+    case 1: d0 = x.y; d1 = x.z; d2 = x.w; d3 = y.x; d4 = y.y; break;
+    case 2: d0 = x.z; d1 = x.w; d2 = y.x; d3 = y.y; d4 = y.z; break;
+    default: d0 = x.w; d1 = y.x; d2 = y.y; d3 = y.z; d4 = y.w; break;
+  }
+  return make_uint4(__builtin_amdgcn_alignbyte(d1, d0, s), __builtin_amdgcn_alignbyte(d2, d1, s),
+                    __builtin_amdgcn_alignbyte(d3, d2, s), __builtin_amdgcn_alignbyte(d4, d3, s));
+}
+
 // Store 16 bytes (w) covering global bytes [ga, ga+16) of which only [lo, hi)
 // belong to this block: one dwordx4 store when whole, byte stores at the edges.
 // PBL_STORE16_NT: whole granules as non-temporal stores (the outputs stream
@@ -517,5 +533,12 @@ enum PersistentKernel { kKColPipe = 0, kKMixedCol = 1, kKRowPool = 2, kKColPipeH
 // least 1); 0 on a runtime error.
 uint64_t persistent_grid(hipStream_t st, PersistentKernel k, const void* fn, uint64_t n_units, int* cus_out,
                          int block_threads = kTPB);
+
+// A runtime bool as a template argument: f(std::true_type{}) or
+// f(std::false_type{}), for launching K<true> or K<false>.
+template <class F>
+auto with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 }  // namespace pbl

@@ -130,7 +130,7 @@ __device__ __forceinline__ uint4 granule(gptr<const uint8_t> base, uint32_t sh, 
   const uint4 x4 = make_uint4(x.x, x.y, x.z, x.w);
   if (!sh) return x4;
   const u32x4 y = a[1];
-  return col::funnel16(x4, make_uint4(y.x, y.y, y.z, y.w), sh);
+  return funnel16(x4, make_uint4(y.x, y.y, y.z, y.w), sh);
 }
 
 // One wave per block.  Lane l takes the 16-B granules l, l+64, l+128, ... (each

@@ -1,6 +1,7 @@
 // rowblk_decode.hip — gfx950 decoder for Pebble row-oriented data blocks: the
 // C-ABI entry points (pbl_decode_batch, pbl_size_batch, the offset concat),
-// the launchers, and the helpers every row kernel shares.
+// the launchers and the mixed-batch kernels.  The rules every row kernel
+// shares are in rowblk_core.hip.h.
 //
 // Kernels:
 //   rowblk_pool_kernel   (rowblk_pool.hip.h) the staging-pool kernel
@@ -25,137 +26,11 @@
 
 #include "common.hip.h"
 #include "colblk_block.hip.h"
-
-namespace pbl {
-namespace row {
-
-constexpr int kPad = 16;                  // LDS front pad: segment gathers may start up to 15 B early
-constexpr int kLdsBlkBytes = kPad + 32768 + 32;  // block staging (any 16-B phase of a <=32 KiB block)
-constexpr uint32_t kMaxFastLen = 32768;   // blocks up to this length take the LDS path
-constexpr uint32_t kRestartMask = 0x7fffffffu;
-constexpr uint64_t kTrailerObsoleteMask = ((((uint64_t)1 << 56) - 1) << 8) | 191u;
-constexpr uint64_t kKindInvalid = kKindInvalidTrailer;
-
-// Unaligned LDS access.  gfx950 runs in unaligned access mode (the HSA
-// runtime's default), where one ds_read_b128 / b64 / b32 serves any byte
-// address: a 16-byte gather is one instruction instead of five dword reads
-// and four alignbytes.  Measured on config 2 (same box, A/B): unaligned 16-byte
-// gathers +2.7 % (992 vs 965 GiB/s), unaligned 8-byte header reads in the
-// parse walk -1.5 %; so gathers are unaligned and ld8/le32 stay dword reads
-// (PBL_LDS_UA8 / PBL_LDS_UA16 switch each form for A/B builds).
-typedef u32x4 u32x4_u __attribute__((aligned(1)));
-typedef u32x2 u32x2_u __attribute__((aligned(1)));
-typedef uint32_t u32_u __attribute__((aligned(1)));
-#ifndef PBL_LDS_UA8
-#define PBL_LDS_UA8 0
-#endif
-#ifndef PBL_LDS_UA16
-#define PBL_LDS_UA16 1
-#endif
-
-// 16 bytes at LDS byte address a (any alignment)
-__device__ inline uint4 lds_gather16(lptr<const uint32_t> W, uint32_t a) {
-#if !PBL_LDS_UA16
-  uint32_t q = a >> 2, r = a & 3;
-  uint32_t x0 = W[q], x1 = W[q + 1], x2 = W[q + 2], x3 = W[q + 3], x4 = W[q + 4];
-  return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, r), __builtin_amdgcn_alignbyte(x2, x1, r),
-                    __builtin_amdgcn_alignbyte(x3, x2, r), __builtin_amdgcn_alignbyte(x4, x3, r));
-#else
-  const u32x4 v = *(lptr<const u32x4_u>)(reinterpret_cast<lptr<const uint8_t>>(W) + a);
-  return make_uint4(v.x, v.y, v.z, v.w);
-#endif
-}
-
-// Read-only view of the staged block: its base offset lives in a register.
-struct View;
-__device__ __forceinline__ View lds_view(const void* lds, uint32_t base);
-struct View {
-  lptr<const uint8_t> B;   // LDS bytes (array start)
-  lptr<const uint32_t> W;  // LDS words (array start)
-  uint32_t base;      // byte index of block byte 0 (kPad + shift)
-  __device__ inline uint32_t byte(uint32_t i) const { return B[base + i]; }
-  // 8 block bytes [i, i+8) as a little-endian u64
-  __device__ inline uint64_t ld8(uint32_t i) const {
-#if !PBL_LDS_UA8
-    uint32_t a = base + i, q = a >> 2, r = a & 3;
-    uint32_t x0 = W[q], x1 = W[q + 1], x2 = W[q + 2];
-    uint32_t lo = __builtin_amdgcn_alignbyte(x1, x0, r);
-    uint32_t hi = __builtin_amdgcn_alignbyte(x2, x1, r);
-    return uint64_t(hi) << 32 | lo;
-#else
-    const u32x2 v = *(lptr<const u32x2_u>)(B + base + i);
-    return uint64_t(v.y) << 32 | v.x;
-#endif
-  }
-  __device__ inline uint32_t le32(uint32_t i) const {
-#if !PBL_LDS_UA8
-    uint32_t a = base + i, q = a >> 2, r = a & 3;
-    return __builtin_amdgcn_alignbyte(W[q + 1], W[q], r);
-#else
-    return *(lptr<const u32_u>)(B + base + i);
-#endif
-  }
-  // 16 block bytes starting at block offset i (i may be up to 15 below 0)
-  __device__ inline uint4 ld16(int32_t i) const { return lds_gather16(W, uint32_t(int32_t(base) + i)); }
-};
-
-__device__ __forceinline__ View lds_view(const void* lds, uint32_t base) {
-  return View{to_lds_ptr(reinterpret_cast<const uint8_t*>(lds)), to_lds_ptr(reinterpret_cast<const uint32_t*>(lds)),
-              base};
-}
-
-// mask of the low n bytes of a word, n clamped to [0, 4]
-__device__ inline uint32_t low_bytes(int n) {
-  n = n < 0 ? 0 : n;
-  return n >= 4 ? 0xffffffffu : (1u << (8 * n)) - 1u;
-}
-// byte mask of bytes [a, b) within the 4-byte word k of a 16-byte granule
-__device__ inline uint32_t word_mask(int k, uint32_t a, uint32_t b) {
-  return low_bytes(int(b) - 4 * k) & ~low_bytes(int(a) - 4 * k);
-}
-__device__ inline void merge16(uint4& w, const uint4& v, uint32_t a, uint32_t b) {
-  uint32_t m;
-  m = word_mask(0, a, b); w.x = (w.x & ~m) | (v.x & m);
-  m = word_mask(1, a, b); w.y = (w.y & ~m) | (v.y & m);
-  m = word_mask(2, a, b); w.z = (w.z & ~m) | (v.z & m);
-  m = word_mask(3, a, b); w.w = (w.w & ~m) | (v.w & m);
-}
-
-// varint from LDS (rowblk_iter.go:2020-2038); returns bytes used, 0 if it runs past `end`
-__device__ inline uint32_t lds_varint(const View& V, uint32_t p, uint32_t end, uint32_t* v) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 0; i < 5; i++) {
-    if (p + i >= end) return 0;
-    uint32_t b = V.byte(p + i);
-    if (i == 4) { *v = r | (b << 28); return 5; }
-    if (b < 128) { *v = r | (b << (7 * i)); return i + 1; }
-    r |= (b & 0x7f) << (7 * i);
-  }
-  return 0;
-}
-
+#include "rowblk_core.hip.h"
 #include "rowblk_general.hip.h"
-
-struct LdsRd {  // staged block through the View
-  View V;
-  __device__ uint32_t byte(uint32_t i) const { return V.byte(i); }
-  __device__ uint32_t le32(uint32_t i) const { return V.le32(i); }
-  __device__ uint32_t varint(uint32_t p, uint32_t end, uint32_t* v) const { return lds_varint(V, p, end, v); }
-};
-struct GlbRd {  // unstaged block in global memory
-  const uint8_t* g;
-  __device__ uint32_t byte(uint32_t i) const { return g[i]; }
-  __device__ uint32_t le32(uint32_t i) const { return g_le32(g + i); }
-  __device__ uint32_t varint(uint32_t p, uint32_t end, uint32_t* v) const { return g_varint(g + p, g + end, v); }
-};
-
 #include "rowblk_big.hip.h"
 #include "rowblk_pool.hip.h"
 #include "rowblk_wave.hip.h"
-
-}  // namespace row
-}  // namespace pbl
 
 #define PBL_COL_PIPE_BODY_ONLY
 #include "colblk_pipe.hip.h"
@@ -363,26 +238,33 @@ void launch_big_values(const pbl::Args& a, hipStream_t st, uint32_t small) {
   hipLaunchKernelGGL(pbl::row::rowc::big_block_values_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
 }
 
-// Row batches on the staging-pool kernel (rowblk_pool.hip.h), with the same
-// big-block passes around it.
+// The staging-pool kernel (rowblk_pool.hip.h): its persistent grid, and its
+// launch over every block or over the row ids of a mixed batch.
+uint64_t pool_grid(hipStream_t st, bool hide, uint32_t nb, int* cus) {
+  namespace pool = pbl::row::pool;
+  const void* fn = pbl::with_bool(
+      hide, [](auto h) { return reinterpret_cast<const void*>(pool::rowblk_pool_kernel<decltype(h)::value>); });
+  return pbl::persistent_grid(st, pbl::kKRowPool, fn, (uint64_t(nb) + pool::kNW - 1) / pool::kNW, cus, pool::kTPBP);
+}
+
+void launch_pool(const pbl::Args& a, hipStream_t st, bool hide, uint64_t grid, const uint32_t* ids) {
+  namespace pool = pbl::row::pool;
+  pbl::with_bool(hide, [&](auto h) {
+    hipLaunchKernelGGL(pool::rowblk_pool_kernel<decltype(h)::value>, dim3(uint32_t(grid)), dim3(pool::kTPBP), 0, st, a,
+                       ids);
+  });
+}
+
+// Row batches on the staging-pool kernel, with the big-block passes around it.
 int launch_row_pool(const pbl::Args& a, hipStream_t st, bool values) {
   const uint32_t nb = a.in.n_blocks;
   const bool hide = (a.in.flags & PBL_ROW_HIDE_OBSOLETE) && !(a.in.flags & PBL_ROW_RAW_KEYS);
-  const void* fn = hide ? reinterpret_cast<const void*>(pbl::row::pool::rowblk_pool_kernel<true>)
-                        : reinterpret_cast<const void*>(pbl::row::pool::rowblk_pool_kernel<false>);
   int cus = 0;
-  const uint64_t grid = pbl::persistent_grid(st, pbl::kKRowPool, fn,
-                                             (uint64_t(nb) + pbl::row::pool::kNW - 1) / pbl::row::pool::kNW, &cus,
-                                             pbl::row::pool::kTPBP);
+  const uint64_t grid = pool_grid(st, hide, nb, &cus);
   if (!grid) return PBL_DEVICE_ERROR;
   const uint32_t small = uint32_t(std::min<uint64_t>(nb, uint64_t(cus > 0 ? cus : 1) * 4));
   launch_big_sizes(a, st, small);
-  if (hide)
-    hipLaunchKernelGGL(pbl::row::pool::rowblk_pool_kernel<true>, dim3(uint32_t(grid)), dim3(pbl::row::pool::kTPBP), 0,
-                       st, a, static_cast<const uint32_t*>(nullptr));
-  else
-    hipLaunchKernelGGL(pbl::row::pool::rowblk_pool_kernel<false>, dim3(uint32_t(grid)), dim3(pbl::row::pool::kTPBP),
-                       0, st, a, static_cast<const uint32_t*>(nullptr));
+  launch_pool(a, st, hide, grid, nullptr);
   if (values) launch_big_values(a, st, small);
   return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
 }
@@ -404,8 +286,8 @@ int launch_mixed(const pbl_block_batch* batch, const pbl::Args& a, hipStream_t s
   hipLaunchKernelGGL(pbl::row::mixed_split_scatter_kernel, dim3(nch), dim3(pbl::kTPB), 0, st, a,
                      static_cast<const uint32_t*>(counts), nch, ids);
   int cus = 0;
-  const void* cfn = hide ? reinterpret_cast<const void*>(pbl::row::mixed_col_kernel<true>)
-                         : reinterpret_cast<const void*>(pbl::row::mixed_col_kernel<false>);
+  const void* cfn = pbl::with_bool(
+      hide, [](auto h) { return reinterpret_cast<const void*>(pbl::row::mixed_col_kernel<decltype(h)::value>); });
   const uint64_t g_c = pbl::persistent_grid(st, hide ? pbl::kKMixedColHide : pbl::kKMixedCol, cfn, nb, &cus);
   if (!g_c) return PBL_DEVICE_ERROR;
   const uint32_t small = uint32_t(std::min<uint64_t>(nb, uint64_t(cus > 0 ? cus : 1) * 4));
@@ -413,38 +295,28 @@ int launch_mixed(const pbl_block_batch* batch, const pbl::Args& a, hipStream_t s
   launch_big_sizes(a, st, small);
   // (3) the colblk sizes, published (the staged wave form, colblk_wave.hip.h)
   const uint32_t g_cs = uint32_t(std::min<uint64_t>(nb, uint64_t(cus > 0 ? cus : 1) * 4 * PBL_CW_SWAVES));
-  if (hide)
-    hipLaunchKernelGGL((pbl::col::cwave::colblk_wave_size_kernel<true, true>), dim3(g_cs), dim3(pbl::kWave), 0, st, a,
-                       cids);
-  else
-    hipLaunchKernelGGL((pbl::col::cwave::colblk_wave_size_kernel<true, false>), dim3(g_cs), dim3(pbl::kWave), 0, st,
-                       a, cids);
+  pbl::with_bool(hide, [&](auto h) {
+    hipLaunchKernelGGL((pbl::col::cwave::colblk_wave_size_kernel<true, decltype(h)::value>), dim3(g_cs),
+                       dim3(pbl::kWave), 0, st, a, cids);
+  });
   // the row blocks on the staging-pool kernel, over the row id list
-  const void* pfn = hide_rows ? reinterpret_cast<const void*>(pbl::row::pool::rowblk_pool_kernel<true>)
-                              : reinterpret_cast<const void*>(pbl::row::pool::rowblk_pool_kernel<false>);
-  const uint64_t g_p = pbl::persistent_grid(st, pbl::kKRowPool, pfn,
-                                            (uint64_t(nb) + pbl::row::pool::kNW - 1) / pbl::row::pool::kNW, &cus,
-                                            pbl::row::pool::kTPBP);
+  const uint64_t g_p = pool_grid(st, hide_rows, nb, &cus);
   if (!g_p) return PBL_DEVICE_ERROR;
-  if (hide_rows)
-    hipLaunchKernelGGL(pbl::row::pool::rowblk_pool_kernel<true>, dim3(uint32_t(g_p)), dim3(pbl::row::pool::kTPBP), 0,
-                       st, a, cids);
-  else
-    hipLaunchKernelGGL(pbl::row::pool::rowblk_pool_kernel<false>, dim3(uint32_t(g_p)), dim3(pbl::row::pool::kTPBP), 0,
-                       st, a, cids);
+  launch_pool(a, st, hide_rows, g_p, cids);
   // (5) the colblk blocks: with HideObsoletePoints the pipeline's fused form;
   // else the wave form's emit over the colblk list, whose look-back finds
   // every predecessor published (the row kernel has finished)
 #ifndef PBL_MIX_COL_WAVE
 #define PBL_MIX_COL_WAVE 1
 #endif
-  if (hide)
-    hipLaunchKernelGGL(pbl::row::mixed_col_kernel<true>, dim3(uint32_t(g_c)), dim3(pbl::kTPB), 0, st, a, cids);
-  else if (PBL_MIX_COL_WAVE)
+  if (!hide && PBL_MIX_COL_WAVE)
     hipLaunchKernelGGL((pbl::col::cwave::colblk_wave_emit_kernel<PBL_CW_STAGE, true>), dim3(nb), dim3(pbl::kWave), 0,
                        st, a, cids);
   else
-    hipLaunchKernelGGL(pbl::row::mixed_col_kernel<false>, dim3(uint32_t(g_c)), dim3(pbl::kTPB), 0, st, a, cids);
+    pbl::with_bool(hide, [&](auto h) {
+      hipLaunchKernelGGL(pbl::row::mixed_col_kernel<decltype(h)::value>, dim3(uint32_t(g_c)), dim3(pbl::kTPB), 0, st,
+                         a, cids);
+    });
   if (values) launch_big_values(a, st, small);
   return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
 }
@@ -477,6 +349,18 @@ int launch_row(const pbl::Args& a, hipStream_t st, bool values) {
     return launch_row_wave(a, st);
   return launch_row_pool(a, st, values);
 }
+
+// The argument checks pbl_decode_batch and pbl_size_batch share: the batch and
+// the per-block outputs (all an empty batch needs), then the inputs and the
+// workspace of a batch with blocks.
+bool per_block_args_ok(const pbl_block_batch* batch, const pbl_decode_out* out) {
+  return batch && out && !(batch->synthetic_seq_num >> 56) &&  // (base.SeqNumMax)
+         out->totals && out->blk_kv_base && out->blk_key_base && out->blk_val_base && out->blk_status;
+}
+bool block_args_ok(const pbl_block_batch* batch, const pbl_decode_out* out) {
+  return batch->blocks && batch->block_off && batch->block_len && out->workspace &&
+         out->workspace_bytes >= pbl::ws_alloc_bytes(batch->n_blocks);
+}
 }  // namespace
 
 extern "C" {
@@ -488,15 +372,12 @@ uint64_t pbl_workspace_bytes(uint32_t n_blocks) { return pbl::ws_alloc_bytes(n_b
 int pbl_decode_batch_colblk(const pbl_block_batch* batch, pbl_decode_out* out, void* stream);
 
 int pbl_decode_batch(const pbl_block_batch* batch, pbl_decode_out* out, void* stream) {
-  if (!batch || !out || (batch->synthetic_seq_num >> 56)) return PBL_INVALID_ARG;  // (base.SeqNumMax)
+  if (!per_block_args_ok(batch, out)) return PBL_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!out->totals || !out->blk_kv_base || !out->blk_key_base || !out->blk_val_base || !out->blk_status)
-    return PBL_INVALID_ARG;
   if (hipMemsetAsync(out->totals, 0, sizeof(pbl_totals), st) != hipSuccess) return PBL_DEVICE_ERROR;
   if (batch->n_blocks == 0) return PBL_OK;
-  if (!batch->blocks || !batch->block_off || !batch->block_len || !out->trailer || !out->key_off ||
-      !out->val_off || !out->key_bytes || !out->val_bytes || !out->workspace ||
-      out->workspace_bytes < pbl::ws_alloc_bytes(batch->n_blocks) || (!out->tiering_span_id != !out->tiering_attr))
+  if (!block_args_ok(batch, out) || !out->trailer || !out->key_off || !out->val_off || !out->key_bytes || !out->val_bytes ||
+      (!out->tiering_span_id != !out->tiering_attr))
     return PBL_INVALID_ARG;
   if (!batch->block_format && batch->format != PBL_FMT_ROW) return pbl_decode_batch_colblk(batch, out, stream);
   if (hipMemsetAsync(out->workspace, 0, pbl::ws_bytes(batch->n_blocks), st) != hipSuccess)
@@ -512,14 +393,10 @@ int pbl_decode_batch(const pbl_block_batch* batch, pbl_decode_out* out, void* st
 }
 
 int pbl_size_batch(const pbl_block_batch* batch, pbl_decode_out* out, void* stream) {
-  if (!batch || !out || (batch->synthetic_seq_num >> 56)) return PBL_INVALID_ARG;
-  if (!out->totals || !out->blk_kv_base || !out->blk_key_base || !out->blk_val_base || !out->blk_status)
-    return PBL_INVALID_ARG;
+  if (!per_block_args_ok(batch, out)) return PBL_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (batch->n_blocks == 0) return pbl_decode_batch(batch, out, stream);
-  if (!batch->blocks || !batch->block_off || !batch->block_len || !out->workspace ||
-      out->workspace_bytes < pbl::ws_alloc_bytes(batch->n_blocks))
-    return PBL_INVALID_ARG;
+  if (!block_args_ok(batch, out)) return PBL_INVALID_ARG;
   // the decode with every per-KV pointer NULL and zero capacities: each block
   // takes its overflow branch (sizes computed and published, nothing written);
   // the fixup then reports the statuses the decode would have had

@@ -1,118 +1,20 @@
-// rowblk_general.hip.h — the general (non-LDS-fast-path) row-block decoder and
-// the per-block metadata helpers shared by both paths.  Included by
-// rowblk_decode.hip inside namespace pbl::row (needs Args, kTrailerObsoleteMask,
-// kKindInvalid, kRestartMask).
+// rowblk_general.hip.h — slow_walk: the general (non-fast-path) row-block
+// decoder, a wave-serial restatement of Iter.First/Next (rowblk_iter.go).  Block
+// bytes come through a reader of rowblk_core.hip.h (LdsBlk when staged, else
+// GlbBlk); the current key lives in an LDS key buffer.  One wave executes it.
 #pragma once
 
+#include <type_traits>
 
-// ---------------------------------------------------------------------------
-// General path: a wave-serial restatement of Iter.First/Next (block bytes read
-// through a generic pointer: LDS when staged, else global), current key in LDS.
-// Executed by wave 0 only.
-// ---------------------------------------------------------------------------
+#include "rowblk_core.hip.h"
+
+namespace pbl {
+namespace row {
+
 struct SlowState {
   uint64_t nkv, kb, vb, nr;
   uint32_t status;
 };
-
-__device__ inline uint32_t g_varint(const uint8_t* p, const uint8_t* end, uint32_t* v) {
-  uint32_t r = 0;
-  for (int i = 0; i < 5; i++) {
-    if (p + i >= end) return 0;
-    uint32_t b = p[i];
-    if (i == 4) { *v = r | (b << 28); return 5; }
-    if (b < 128) { *v = r | (b << (7 * i)); return i + 1; }
-    r |= (b & 0x7f) << (7 * i);
-  }
-  return 0;
-}
-
-__device__ inline uint32_t g_le32(const uint8_t* p) {
-  return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
-}
-
-// Block sources of the general path.  Both read bytes, LE32 words and 16-byte
-// windows at block offsets; an ld16 window may start up to 15 bytes before the
-// block or end past it (those bytes are don't-cares; nothing outside the
-// block's 16-B granules is touched).  Typed address spaces throughout: a
-// generic (FLAT) LDS read would wait for every outstanding global store.
-struct SlowLds {  // block staged in LDS (byte 0 at B[base])
-  View V;
-  __device__ __forceinline__ uint32_t byte(uint64_t i) const { return V.byte(uint32_t(i)); }
-  __device__ __forceinline__ uint32_t le32(uint64_t i) const { return V.le32(uint32_t(i)); }
-  __device__ __forceinline__ uint4 ld16(int64_t i) const { return V.ld16(int32_t(i)); }
-};
-struct SlowGlb {  // block in global memory
-  gptr<const uint8_t> g;
-  uint64_t len;
-  __device__ __forceinline__ uint32_t byte(uint64_t i) const { return g[i]; }
-  __device__ __forceinline__ uint32_t le32(uint64_t i) const {
-    return uint32_t(g[i]) | uint32_t(g[i + 1]) << 8 | uint32_t(g[i + 2]) << 16 | uint32_t(g[i + 3]) << 24;
-  }
-  __device__ __forceinline__ uint4 ld16(int64_t i) const {
-    const uint64_t s0 = uint64_t(g), s1 = s0 + len, sx = s0 + uint64_t(i), sa = sx & ~uint64_t(15);
-    const uint32_t sh = uint32_t(sx - sa);
-    uint4 x = make_uint4(0, 0, 0, 0), y = make_uint4(0, 0, 0, 0);
-    if (sa + 16 > s0 && sa < s1) {
-      const u32x4 v = *(gptr<const u32x4>)(sa);
-      x = make_uint4(v.x, v.y, v.z, v.w);
-    }
-    if (sh && sa + 32 > s0 && sa + 16 < s1) {
-      const u32x4 v = *(gptr<const u32x4>)(sa + 16);
-      y = make_uint4(v.x, v.y, v.z, v.w);
-    }
-    return sh ? col::funnel16(x, y, sh) : x;
-  }
-  // Block bytes from offset v -> out[lo, hi), 16-B destination granules, U per
-  // lane in flight.  Every granule's two source loads are issued before any is
-  // used, at addresses clamped to the block's own granules (those bytes feed
-  // only masked destination bytes); the shift is one per value.  Through ld16
-  // each granule's guarded loads and funnel waited in turn: config 5's
-  // big-block values pass, one 48 KB value per block, took 125 us.
-  template <int U>
-  __device__ __forceinline__ void copy(uint64_t v, uint8_t* out, uint64_t lo, uint64_t hi) const {
-    const uint64_t s0 = uint64_t(g), g_lo = s0 & ~uint64_t(15), g_hi = (s0 + len - 1) & ~uint64_t(15);
-    const uint64_t d = s0 + v - lo;  // source address of destination offset ga: d + ga
-    const uint32_t sh = __builtin_amdgcn_readfirstlane(uint32_t(d) & 15u);
-    for (uint64_t g0 = (lo & ~uint64_t(15)) + 16ull * lane_id(); g0 < hi; g0 += 16ull * kWave * U) {
-      u32x4 x[U], y[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint64_t sa = (d + g0 + 16ull * kWave * u) & ~uint64_t(15);
-        x[u] = *(gptr<const u32x4>)(min(max(sa, g_lo), g_hi));
-        if (sh) y[u] = *(gptr<const u32x4>)(min(max(sa + 16, g_lo), g_hi));
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint64_t ga = g0 + 16ull * kWave * u;
-        const uint4 a = make_uint4(x[u].x, x[u].y, x[u].z, x[u].w);
-        if (ga < hi)
-          store16(out, ga, lo, hi, sh ? col::funnel16(a, make_uint4(y[u].x, y[u].y, y[u].z, y[u].w), sh) : a);
-      }
-    }
-  }
-};
-
-// byte k (< 16) of a 16-byte window, by shifts (a runtime-indexed register
-// array would live in scratch)
-__device__ __forceinline__ uint32_t win_byte(const uint4& w, uint32_t k) {
-  const uint64_t q = k < 8 ? (uint64_t(w.x) | uint64_t(w.y) << 32) : (uint64_t(w.z) | uint64_t(w.w) << 32);
-  return uint32_t(q >> (8 * (k & 7))) & 0xffu;
-}
-
-// varint at window bytes [i0, n) (g_varint's rules: 5th byte << 28, none past n)
-__device__ __forceinline__ uint32_t w_varint(const uint4& w, uint32_t i0, uint32_t n, uint32_t* v) {
-  uint32_t r = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 5; i++) {
-    if (i0 + i >= n) return 0;
-    const uint32_t b = win_byte(w, i0 + i);
-    if (i == 4) { *v = r | (b << 28); return 5; }
-    if (b < 128) { *v = r | (b << (7 * i)); return i + 1; }
-    r |= (b & 0x7f) << (7 * i);
-  }
-  return 0;
-}
 
 // Key buffer: LDS bytes with a 16-B front pad and a 32-B tail so that 16-B
 // gathers around the key stay inside it.
@@ -147,19 +49,17 @@ __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t 
   uint32_t status = PBL_OK;
   // the next entry's header window is loaded before this entry's stores: a
   // load's data waits for every older vector-memory op, so a header read
-  // behind the value stores would wait for all of them (config 5's values walk:
-  // see rowblk_global.hip.h)
+  // behind the value stores would wait for all of them (config 5's big-block
+  // values walk)
   uint4 hw_next = restarts > 0 ? S.ld16(0) : make_uint4(0, 0, 0, 0);
   while (offset >= 0 && offset < restarts) {
     // the header's bytes in one window, the three varints from registers
     const uint4 hw = hw_next;
     const uint32_t hn = uint32_t(min<int64_t>(15, int64_t(len) - offset));
     uint32_t shared, unshared, vlen;
-    const uint32_t a = w_varint(hw, 0, hn, &shared);
-    const uint32_t bb = a ? w_varint(hw, a, hn, &unshared) : 0;
-    const uint32_t c = bb ? w_varint(hw, a + bb, hn, &vlen) : 0;
-    if (!c) { status = PBL_CORRUPT_BOUNDS; break; }
-    const uint64_t kp = uint64_t(offset) + a + bb + c;
+    const uint32_t h = entry_header(hw, hn, &shared, &unshared, &vlen);
+    if (!h) { status = PBL_CORRUPT_BOUNDS; break; }
+    const uint64_t kp = uint64_t(offset) + h;
     if (len - kp < unshared) { status = PBL_CORRUPT_BOUNDS; break; }
     const uint64_t vp = kp + unshared;
     if (len - vp < vlen) { status = PBL_CORRUPT_BOUNDS; break; }
@@ -178,23 +78,13 @@ __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t 
     }
     wave_sync();
     full_len = klen;
-    uint64_t trailer, ukl;
-    uint8_t fl = 0;
-    if (flags & PBL_ROW_RAW_KEYS) {
-      trailer = 0;
-      ukl = klen;
-    } else if (klen >= 8) {
-      uint64_t raw = 0;
+    uint64_t trailer, ukl, raw = 0;
+    uint32_t fl = 0;
+    if (!(flags & PBL_ROW_RAW_KEYS) && klen >= 8) {
 #pragma unroll
       for (int i = 0; i < 8; i++) raw |= uint64_t(keybuf[klen - 8 + i]) << (8 * i);
-      if (raw & 64u) fl |= PBL_KV_OBSOLETE;
-      trailer = raw & kTrailerObsoleteMask;
-      ukl = klen - 8;
-    } else {
-      trailer = kKindInvalid;
-      ukl = 0;
-      fl |= PBL_KV_INVALID_KEY;
     }
+    split_trailer(raw, klen, flags, &trailer, &ukl, &fl);
     // blockiter.Transforms.HideObsoletePoints: the entry is skipped before its
     // value is looked at (rowblk_iter.go:1168-1179); its key still feeds the
     // prefix compression of the entries after it
@@ -205,10 +95,10 @@ __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t 
     uint64_t v = vp, vl = vlen;
     if ((flags & PBL_ROW_VALUE_PREFIX) && !(flags & PBL_ROW_RAW_KEYS) && (trailer & 0xff) == 1) {
       if (vl == 0) { status = PBL_CORRUPT_BOUNDS; break; }
-      const uint32_t pre = S.byte(v);
-      if ((pre & 0xC0) == 0 || (flags & PBL_ROW_NO_VALUER)) { v++; vl--; }
-      else if ((pre & 0xC0) == 0x80) fl |= PBL_KV_VALBLK_HANDLE;
-      else fl |= PBL_KV_BLOB_HANDLE;
+      uint32_t skip;
+      value_prefix(S.byte(v), flags, &skip, &fl);
+      v += skip;
+      vl -= skip;
     }
     if (pass == kPassAll) {
       while (ri < uint32_t(nr) && int64_t(rw_ri & kRestartMask) < offset) {
@@ -225,7 +115,7 @@ __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t 
       const uint64_t kv = bases[0] + nkv, o = bases[0] + b + nkv;
       if (l == 0) {
         o_trailer[kv] = with_seq(trailer, seq, flags);
-        if (O.kv_flags) o_flags[kv] = fl;
+        if (O.kv_flags) o_flags[kv] = uint8_t(fl);
         if (O.entry_off) o_entry[kv] = uint32_t(offset);
         o_koff[o] = uint32_t(kb);
         o_voff[o] = uint32_t(vb);
@@ -240,7 +130,7 @@ __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t 
     if (pass == kPassAll) {
       // value: 16-B destination granules from source windows, U per lane in flight
       const uint64_t lo = bases[2] + vb, hi = lo + vl;
-      if constexpr (std::is_same<Src, SlowGlb>::value) {
+      if constexpr (std::is_same<Src, GlbBlk>::value) {
         S.template copy<U>(v, O.val_bytes, lo, hi);
       } else {
         for (uint64_t g0 = (lo & ~uint64_t(15)) + 16ull * l; g0 < hi; g0 += 16ull * kWave * U) {
@@ -291,11 +181,12 @@ __device__ __noinline__ void slow_walk(const uint8_t* blk, bool blk_lds, uint64_
     // start up to 15 bytes early; the staging buffers carry a 16-B front pad)
     const uint32_t a = uint32_t(uint64_t(to_lds_ptr(blk)));
     const uint32_t base = 16u + (a & 15u);
-    slow_walk_t<SlowLds, PBL_SLOW_U>(SlowLds{lds_view(reinterpret_cast<const void*>(blk - base), base)}, len, flags,
+    slow_walk_t<LdsBlk, PBL_SLOW_U>(LdsBlk{lds_view(reinterpret_cast<const void*>(blk - base), base)}, len, flags,
                                      seq, kbuf, keycap, pass, O, b, bases, st);
   } else {
-    slow_walk_t<SlowGlb, PBL_SLOW_U>(SlowGlb{to_glb(blk), len}, len, flags, seq, kbuf, keycap, pass, O, b, bases, st);
+    slow_walk_t<GlbBlk, PBL_SLOW_U>(GlbBlk{to_glb(blk), len}, len, flags, seq, kbuf, keycap, pass, O, b, bases, st);
   }
 }
 
-
+}  // namespace row
+}  // namespace pbl

@@ -43,6 +43,12 @@
 // HideObsoletePoints :1168-1179.
 #pragma once
 
+#include "rowblk_core.hip.h"
+#include "rowblk_general.hip.h"
+#include "rowblk_big.hip.h"
+
+namespace pbl {
+namespace row {
 namespace pool {
 
 #ifndef PBL_POOL_WAVES
@@ -179,7 +185,7 @@ __device__ __forceinline__ uint4 gld16(gptr<const uint8_t> g, int32_t i, uint32_
     const u32x4 v = *(gptr<const u32x4_ug>)(g + i);
     return make_uint4(v.x, v.y, v.z, v.w);
   }
-  return SlowGlb{g, blen}.ld16(i);
+  return GlbBlk{g, blen}.ld16(i);
 }
 
 // ---- the walk: lane per restart run ------------------------------------------
@@ -238,7 +244,7 @@ __device__ __forceinline__ void count_span(const View& V, uint32_t pos, uint32_t
                                            bool& bad, bool& vbad) {
   while (pos < e0) {
     uint32_t sh, un, vl, h;
-    const bool hok = rowc::hdr2(V.ld8(pos), &sh, &un, &vl, &h);
+    const bool hok = hdr2(V.ld8(pos), &sh, &un, &vl, &h);
     const uint32_t np = pos + h + un + vl;  // < 2^23: no overflow
     if (!hok || (k == 0 && sh != 0) || np > e0) { ok = false; return; }
     bad = bad || (k > 0 && sh > prev_kl);
@@ -289,7 +295,7 @@ __device__ __forceinline__ void run_walk(const View& V, uint32_t r, uint32_t nre
   for (int k = 0; k < kRunBuf; k++) {
     if (go && pos < e0) {
       uint32_t sh, un, vl, h;
-      const bool hok = rowc::hdr2(V.ld8(pos), &sh, &un, &vl, &h);
+      const bool hok = hdr2(V.ld8(pos), &sh, &un, &vl, &h);
       const uint32_t np = pos + h + un + vl;
       bool hidden = false, setv = false;
       if (!hok || (k == 0 && sh != 0) || np > e0) {
@@ -398,7 +404,7 @@ __device__ __forceinline__ void span_meta(Slot<kHide>& W, const View& V, uint32_
                                           bool vprefix, MState& M) {
   while (pos < e0) {
     uint32_t sh, un, vl, h;
-    rowc::hdr2(V.ld8(pos), &sh, &un, &vl, &h);
+    hdr2(V.ld8(pos), &sh, &un, &vl, &h);
     const uint32_t kl = sh + un;
     bool hidden, setv;
     entry_class<kHide>(V, pos, h, sh, kl, k, prev_kl, prev_kind, flags, vprefix, hidden, setv);
@@ -406,6 +412,45 @@ __device__ __forceinline__ void span_meta(Slot<kHide>& W, const View& V, uint32_
     k++;
     prev_kl = kl;
     pos = pos + h + un + vl;
+  }
+}
+
+// A lane's runs [r0, r1) walked and counted into acc.  `single` (one run per
+// lane at most): the run's head is parked in RB; a run longer than kRunBuf
+// keeps its parked head and counts only its tail.
+template <bool kHide>
+__device__ __forceinline__ void walk_runs(const View& V, uint32_t r0, uint32_t r1, uint32_t nres, uint32_t roff,
+                                          uint32_t flags, bool vprefix, bool single, PRun& RB, PAcc& acc, bool& ok,
+                                          bool& bad, bool& vbad, bool& over) {
+  if (single) {
+    if (r0 < nres) run_walk<kHide>(V, r0, nres, roff, flags, vprefix, RB, acc, ok, bad, vbad, over);
+    if (over && ok)
+      count_span<kHide>(V, RB.pos, RB.e0, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, acc, ok, bad, vbad);
+    return;
+  }
+  for (uint32_t r = r0; r < r1 && ok; r++) {
+    uint32_t rw, e0;
+    if (!run_bounds(V, r, nres, roff, &rw, &e0)) ok = false;
+    else count_span<kHide>(V, rw & kRestartMask, e0, 0, 0, 0, flags, vprefix, acc, ok, bad, vbad);
+  }
+}
+
+// The metadata of the runs walk_runs accepted, M placed at the lane's first entry.
+template <bool kHide>
+__device__ __forceinline__ void meta_runs(Slot<kHide>& W, const View& V, uint32_t r0, uint32_t r1, uint32_t nres,
+                                          uint32_t roff, uint32_t flags, bool vprefix, bool single, bool over,
+                                          const PRun& RB, MState& M) {
+  if (single) {
+    if (r0 >= nres) return;
+    park_meta<kHide>(W, V, RB, flags, M);
+    if (over) span_meta<kHide>(W, V, RB.pos, RB.e0, RB.rw, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, M);
+    return;
+  }
+  for (uint32_t r = r0; r < r1; r++) {
+    uint32_t rw, e0;
+    run_bounds(V, r, nres, roff, &rw, &e0);
+    M.prev_sh = M.pp = M.ppsh = 0;
+    span_meta<kHide>(W, V, rw & kRestartMask, e0, rw, 0, 0, 0, flags, vprefix, M);
   }
 }
 
@@ -431,19 +476,15 @@ __device__ __forceinline__ uint32_t key_byte(const uint64_t* M0, const Src& V, i
 template <class Src>
 __device__ __forceinline__ uint64_t trailer_of(const uint64_t* M0, const Src& V, int j, uint64_t m, uint32_t* fl,
                                                uint32_t flags) {
-  if (flags & PBL_ROW_RAW_KEYS) return 0;
-  const uint32_t kl = m_klen(m);
-  if (kl < 8) return kKindInvalid;
-  const uint32_t sh = m_sh(m);
-  uint64_t raw;
-  if (kl - 8 >= sh) {
-    raw = V.ld8(m_ksrc(m) + (kl - 8 - sh));
-  } else {
-    raw = 0;
-    for (int i = 0; i < 8; i++) raw |= uint64_t(key_byte(M0, V, j, kl - 8 + i)) << (8 * i);
+  const uint32_t kl = m_klen(m), sh = m_sh(m);
+  uint64_t raw = 0, t, ukl;
+  if (!(flags & PBL_ROW_RAW_KEYS) && kl >= 8) {
+    if (kl - 8 >= sh) raw = V.ld8(m_ksrc(m) + (kl - 8 - sh));
+    else
+      for (int i = 0; i < 8; i++) raw |= uint64_t(key_byte(M0, V, j, kl - 8 + i)) << (8 * i);
   }
-  if (raw & 64u) *fl |= PBL_KV_OBSOLETE;
-  return raw & kTrailerObsoleteMask;
+  split_trailer(raw, kl, flags, &t, &ukl, fl);
+  return t;
 }
 
 // Key bytes [c, c + n) of KV m (n <= 16) merged from the segments of its prefix
@@ -628,12 +669,8 @@ __device__ __forceinline__ void key_store(const Slot<kHide>& W, const Src& V, co
       t = trailer_of(W.m0, V, int(e), m, &f, flags);
       store_key_general(W.m0, V, m, ukl, kbytes + ko);
     } else {
-      if (raw) t = 0;
-      else if (kl < 8) t = kKindInvalid;
-      else {
-        if (K.tr[u] & 64u) f |= PBL_KV_OBSOLETE;
-        t = K.tr[u] & kTrailerObsoleteMask;
-      }
+      uint64_t tukl;
+      split_trailer(K.tr[u], kl, flags, &t, &tukl, &f);
       if (ukl) {
         const uint32_t lo = sh < ukl ? sh : ukl;
         uint4 w = K.ka[u];
@@ -951,7 +988,7 @@ __device__ __noinline__ void block_big(const Args A, uint32_t b, uint64_t boff, 
   const bool okk = st0 == PBL_OK;
   const uint64_t agg[kNumComp] = {okk ? to_glb(O.blk_kv_base)[b] : 0, okk ? to_glb(O.blk_key_base)[b] : 0,
                                   okk ? to_glb(O.blk_val_base)[b] : 0,
-                                  okk ? uint64_t(SlowGlb{to_glb(A.in.blocks + boff), blen}.le32(blen - 4)) : 0};
+                                  okk ? uint64_t(GlbBlk{to_glb(A.in.blocks + boff), blen}.le32(blen - 4)) : 0};
   uint64_t excl[kNumComp];
   lb_resolve(lb_state, nb, b, agg, excl, &O.totals->status_mask);
   uint32_t st2 = st0;
@@ -965,7 +1002,7 @@ __device__ __noinline__ void block_big(const Args A, uint32_t b, uint64_t boff, 
   }
   if (st2 == PBL_OK) {
     SlowState ss;
-    slow_walk_t<SlowGlb, PBL_BIG_U>(SlowGlb{to_glb(A.in.blocks + boff), blen}, blen, A.in.flags,
+    slow_walk_t<GlbBlk, PBL_BIG_U>(GlbBlk{to_glb(A.in.blocks + boff), blen}, blen, A.in.flags,
                                     A.in.synthetic_seq_num, to_lds_ptr(keybuf), keycap, kPassAll, O, b, excl, &ss);
     if (ss.status == PBL_UNSUPPORTED && l == 0) {  // a key past the slot: the values pass rewrites the block
       uint32_t* hdr = reinterpret_cast<uint32_t*>(O.workspace);
@@ -1021,7 +1058,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
   PSTAMP(A, b, 2, l == 0);
   const View V = lds_view(S.x, uint32_t(kPad + (boff & 15)));
   uint32_t roff, nres;
-  uint32_t status = rowc::init_checks(LdsRd{V}, blen, flags, &roff, &nres);
+  uint32_t status = init_checks(LdsBlk{V}, blen, flags, &roff, &nres);
   bool slow = status == PBL_OK && nres > kKv;
   uint32_t nkv = 0, tkb = 0, tvb = 0;
   bool published = false;
@@ -1035,18 +1072,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
     RB.n = 0;
     RB.pos = RB.e0 = RB.prev_kl = RB.prev_kind = RB.rw = 0;
     const bool single = R == 1;
-    if (single) {
-      if (r0 < nres) run_walk<kHide>(V, r0, nres, roff, flags, vprefix, RB, acc, ok, bad, vbad, over);
-      // a run longer than kRunBuf keeps its parked head and counts only its tail
-      if (over && ok)
-        count_span<kHide>(V, RB.pos, RB.e0, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, acc, ok, bad, vbad);
-    } else {
-      for (uint32_t r = r0; r < r1 && ok; r++) {
-        uint32_t rw, e0;
-        if (!run_bounds(V, r, nres, roff, &rw, &e0)) ok = false;
-        else count_span<kHide>(V, rw & kRestartMask, e0, 0, 0, 0, flags, vprefix, acc, ok, bad, vbad);
-      }
-    }
+    walk_runs<kHide>(V, r0, r1, nres, roff, flags, vprefix, single, RB, acc, ok, bad, vbad, over);
     const uint32_t ic = dpp_incl_scan(acc.cnt), ik = dpp_incl_scan(acc.kb), iv = dpp_incl_scan(acc.vb);
     const uint32_t ie = kHide ? dpp_incl_scan(acc.ne) : ic;
     nkv = last_lane(ic);
@@ -1063,19 +1089,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
       published = true;
       PSTAMP(A, b, 3, l == 0);
       MState M{ie - (kHide ? acc.ne : acc.cnt), ic - acc.cnt, iv - acc.vb, 0, 0, 0};
-      if (single) {
-        if (r0 < nres) {
-          park_meta<kHide>(W, V, RB, flags, M);
-          if (over) span_meta<kHide>(W, V, RB.pos, RB.e0, RB.rw, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, M);
-        }
-      } else {
-        for (uint32_t r = r0; r < r1; r++) {
-          uint32_t rw, e0;
-          run_bounds(V, r, nres, roff, &rw, &e0);
-          M.prev_sh = M.pp = M.ppsh = 0;
-          span_meta<kHide>(W, V, rw & kRestartMask, e0, rw, 0, 0, 0, flags, vprefix, M);
-        }
-      }
+      meta_runs<kHide>(W, V, r0, r1, nres, roff, flags, vprefix, single, over, RB, M);
       if (l < 5) W.vp[nkv + l] = tvb;
       PSTAMP(A, b, 4, l == 0);
     }
@@ -1249,3 +1263,5 @@ __global__ void __launch_bounds__(kTPBP, 1) rowblk_pool_kernel(Args A, const uin
 }
 
 }  // namespace pool
+}  // namespace row
+}  // namespace pbl

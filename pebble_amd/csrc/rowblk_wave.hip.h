@@ -29,11 +29,18 @@
 // 241-276, readEntry :333-416, the key-buffer limit of the general path); the
 // emit's lane-parallel form is taken only where its walk agrees with those
 // sizes, else the emit IS slow_walk_t.  (The wave-serial walk alone measured
-// 2.87 ms on config 5 RI 16: ~6.9 K cycles per entry of dependent LDS steps.)  Flags that need a key's bytes
-// to size it (HideObsoletePoints, value prefixes, on internal keys) take the
-// pool kernel.
+// 2.87 ms on config 5 RI 16: ~6.9 K cycles per entry of dependent LDS steps.)
+// Flags that need a key's bytes to size it (HideObsoletePoints, value
+// prefixes, on internal keys) take the pool kernel.
 #pragma once
 
+#include "rowblk_core.hip.h"
+#include "rowblk_general.hip.h"
+#include "rowblk_big.hip.h"
+#include "rowblk_pool.hip.h"
+
+namespace pbl {
+namespace row {
 namespace rwave {
 
 #ifndef PBL_RW_VALU
@@ -70,7 +77,7 @@ __device__ __forceinline__ void put_sizes(const pbl_decode_out& O, gptr<uint64_t
 // slow_walk_t's loop from block offset `off` (entries before it counted into
 // nkv / kb / vb, `full` the last key's length), its checks in its order,
 // without the key bytes; at most `limit` entries (then *more is set).
-__device__ __forceinline__ uint32_t seq_count(const SlowGlb& S, uint32_t blen, uint32_t roff, bool raw, uint64_t& off,
+__device__ __forceinline__ uint32_t seq_count(const GlbBlk& S, uint32_t blen, uint32_t roff, bool raw, uint64_t& off,
                                               uint64_t& full, uint64_t& nkv, uint64_t& kb, uint64_t& vb,
                                               uint32_t limit, bool* more, gptr<uint16_t> rec) {
   uint32_t n = 0;
@@ -80,11 +87,9 @@ __device__ __forceinline__ uint32_t seq_count(const SlowGlb& S, uint32_t blen, u
     const uint4 hw = S.ld16(int64_t(off));
     const uint32_t hn = uint32_t(min<uint64_t>(15, uint64_t(blen) - off));
     uint32_t shared, unshared, vlen;
-    const uint32_t a = w_varint(hw, 0, hn, &shared);
-    const uint32_t bb = a ? w_varint(hw, a, hn, &unshared) : 0;
-    const uint32_t c = bb ? w_varint(hw, a + bb, hn, &vlen) : 0;
-    if (!c) return PBL_CORRUPT_BOUNDS;
-    const uint64_t kp = off + a + bb + c;
+    const uint32_t h = entry_header(hw, hn, &shared, &unshared, &vlen);
+    if (!h) return PBL_CORRUPT_BOUNDS;
+    const uint64_t kp = off + h;
     if (blen - kp < unshared) return PBL_CORRUPT_BOUNDS;
     const uint64_t vp = kp + unshared;
     if (blen - vp < vlen) return PBL_CORRUPT_BOUNDS;
@@ -118,10 +123,10 @@ __global__ void __launch_bounds__(kWave) row_wave_size_kernel(Args A) {
       const uint32_t blen = to_glb(A.in.block_len)[b];
       const uint8_t* g = A.in.blocks + to_glb(A.in.block_off)[b];
       uint32_t roff, nres;
-      uint32_t status = rowc::init_checks(GlbRd{g}, blen, flags, &roff, &nres);
+      uint32_t status = init_checks(GlbBlk{to_glb(g), blen}, blen, flags, &roff, &nres);
       uint64_t nkv = 0, kb = 0, vb = 0;
       if (status == PBL_OK) {
-        const SlowGlb S{to_glb(g), blen};
+        const GlbBlk S{to_glb(g), blen};
         const gptr<uint16_t> r = blen <= kMaxFastLen ? rec + b * kEntRec : gptr<uint16_t>(nullptr);
         uint64_t off = 0, full = 0;
         bool more = false;
@@ -172,7 +177,7 @@ __global__ void __launch_bounds__(kWave) row_wave_dense_kernel(Args A) {
     const uint32_t b = dense_ids[i];
     const uint32_t blen = to_glb(A.in.block_len)[b];
     const uint8_t* g = A.in.blocks + to_glb(A.in.block_off)[b];
-    const SlowGlb S{to_glb(g), blen};
+    const GlbBlk S{to_glb(g), blen};
     const uint32_t nres = S.le32(blen - 4), roff = blen - 4u * (1u + nres);  // (the size pass checked them)
     uint64_t nkv = 0, kb = 0, vb = 0;
     bool ok = true;
@@ -185,13 +190,11 @@ __global__ void __launch_bounds__(kWave) row_wave_dense_kernel(Args A) {
       while (off < e0) {
         const uint4 hw = S.ld16(int64_t(off));
         const uint32_t hn = uint32_t(min<uint64_t>(15, uint64_t(blen) - off));
-        uint32_t shared, unshared, vlen;
-        const uint32_t a = w_varint(hw, 0, hn, &shared);
-        const uint32_t bb = a ? w_varint(hw, a, hn, &unshared) : 0;
-        const uint32_t c = bb ? w_varint(hw, a + bb, hn, &vlen) : 0;
-        const uint64_t np = off + a + bb + c + unshared + vlen;
+        uint32_t shared = 0, unshared = 0, vlen = 0;
+        const uint32_t h = entry_header(hw, hn, &shared, &unshared, &vlen);
+        const uint64_t np = off + h + unshared + vlen;
         const uint64_t klen = uint64_t(shared) + unshared;
-        if (!c || np > e0 || (first ? shared != 0 : shared > prev) || klen > kKeyCapMax) { ok = false; break; }
+        if (!h || np > e0 || (first ? shared != 0 : shared > prev) || klen > kKeyCapMax) { ok = false; break; }
         nkv++;
         kb += raw ? klen : (klen >= 8 ? klen - 8 : 0);
         vb += vlen;
@@ -246,7 +249,7 @@ __device__ __forceinline__ bool front_fast(const View& V, uint32_t blen, uint32_
   constexpr uint32_t kKv = uint32_t(Slot<false>::kKv);
   const bool vprefix = (flags & PBL_ROW_VALUE_PREFIX) && !(flags & PBL_ROW_RAW_KEYS);
   uint32_t roff, nres;
-  if (rowc::init_checks(LdsRd{V}, blen, flags, &roff, &nres) != PBL_OK || roff == 0 || nres > kKv) return false;
+  if (init_checks(LdsBlk{V}, blen, flags, &roff, &nres) != PBL_OK || roff == 0 || nres > kKv) return false;
   // lane l owns runs [r0, r1)
   const uint32_t R = (nres + kWave - 1) / kWave;
   const uint32_t r0 = min(uint32_t(l) * R, nres), r1 = min(r0 + R, nres);
@@ -256,35 +259,13 @@ __device__ __forceinline__ bool front_fast(const View& V, uint32_t blen, uint32_
   RB.n = 0;
   RB.pos = RB.e0 = RB.prev_kl = RB.prev_kind = RB.rw = 0;
   const bool single = R == 1;
-  if (single) {
-    if (r0 < nres) run_walk<false>(V, r0, nres, roff, flags, vprefix, RB, acc, ok, bad, vbad, over);
-    if (over && ok)
-      count_span<false>(V, RB.pos, RB.e0, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, acc, ok, bad, vbad);
-  } else {
-    for (uint32_t r = r0; r < r1 && ok; r++) {
-      uint32_t rw, e0;
-      if (!run_bounds(V, r, nres, roff, &rw, &e0)) ok = false;
-      else count_span<false>(V, rw & kRestartMask, e0, 0, 0, 0, flags, vprefix, acc, ok, bad, vbad);
-    }
-  }
+  walk_runs<false>(V, r0, r1, nres, roff, flags, vprefix, single, RB, acc, ok, bad, vbad, over);
   const uint32_t ic = dpp_incl_scan(acc.cnt), ik = dpp_incl_scan(acc.kb), iv = dpp_incl_scan(acc.vb);
   const uint32_t nkv = last_lane(ic), tkb = last_lane(ik), tvb = last_lane(iv);
   if (__ballot(bad || vbad || !ok) || nkv > kKv) return false;
   if (nkv != agg[0] || tkb != agg[1] || tvb != agg[2] || nres != agg[3]) return false;
   MState M{ic - acc.cnt, ic - acc.cnt, iv - acc.vb, 0, 0, 0};
-  if (single) {
-    if (r0 < nres) {
-      park_meta<false>(W, V, RB, flags, M);
-      if (over) span_meta<false>(W, V, RB.pos, RB.e0, RB.rw, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, M);
-    }
-  } else {
-    for (uint32_t r = r0; r < r1; r++) {
-      uint32_t rw, e0;
-      run_bounds(V, r, nres, roff, &rw, &e0);
-      M.prev_sh = M.pp = M.ppsh = 0;
-      span_meta<false>(W, V, rw & kRestartMask, e0, rw, 0, 0, 0, flags, vprefix, M);
-    }
-  }
+  meta_runs<false>(W, V, r0, r1, nres, roff, flags, vprefix, single, over, RB, M);
   if (l < 5) W.vp[nkv + l] = tvb;
   *roff_o = roff;
   return true;
@@ -309,7 +290,7 @@ __device__ __forceinline__ bool front_par(const View& V, uint32_t blen, uint32_t
   uint32_t sh = 0, un = 0, vl = 0, h = 0;
   bool ok = true;
   if (me) {
-    ok = (l != 0 || pos == 0) && rowc::hdr2(V.ld8(pos), &sh, &un, &vl, &h) && sh + un <= kMaxKl && h <= 15;
+    ok = (l != 0 || pos == 0) && hdr2(V.ld8(pos), &sh, &un, &vl, &h) && sh + un <= kMaxKl && h <= 15;
     const uint32_t nxt = __shfl(pos, l + 1 < kWave ? l + 1 : l, kWave);
     ok = ok && pos + h + un + vl == (uint32_t(l) + 1 < nkv ? nxt : roff);
   }
@@ -338,7 +319,8 @@ __device__ __forceinline__ bool front_par(const View& V, uint32_t blen, uint32_t
       const uint32_t rw = V.le32(roff + 4 * lo);
       if ((rw & kRestartMask) == pos) fl = PBL_KV_RESTART | ((rw >> 31) ? PBL_KV_RESTART_SAMEPFX : 0u);
     }
-    if (!raw && kl < 8) fl |= PBL_KV_INVALID_KEY;
+    uint64_t tr, ukl;  // (only PBL_KV_INVALID_KEY here: key_store reads the trailer's bytes)
+    split_trailer(0, kl, flags, &tr, &ukl, &fl);
   }
   const uint32_t incl = dpp_incl_scan(me ? vl : 0u);
   if (me) {
@@ -432,8 +414,9 @@ __device__ __forceinline__ void emit_keys(const Args& A, uint32_t b, const View&
 constexpr int kRwWaves = PBL_RW_WAVES;
 static_assert(kRwWaves >= 1 && kRwWaves <= 3, "emit waves per block: 1 to 3");
 
-// One block's bases, status and extent: SCALAR loads (the constant address
-// space: nothing in this kernel writes them).
+// One block's bases and extent: SCALAR loads (the constant address space:
+// nothing in this kernel writes them).  blk_status is written by emit_block,
+// so it is read with an ordinary global load.
 template <class T>
 using cptr = __attribute__((address_space(4))) const T*;
 struct RDesc {
@@ -454,7 +437,7 @@ __device__ __forceinline__ RDesc load_desc(const Args& A, uint32_t b) {
   const cptr<uint64_t> rc = (cptr<uint64_t>)(ws + ws_rcnt_offset(nb));
   d.r0 = rc[b];
   d.r1 = rc[b + 1];
-  d.status = ((cptr<uint32_t>)O.blk_status)[b];
+  d.status = to_glb(O.blk_status)[b];
   d.boff = ((cptr<uint64_t>)A.in.block_off)[b];
   d.blen = ((cptr<uint32_t>)A.in.block_len)[b];
   return d;
@@ -547,14 +530,14 @@ __device__ __forceinline__ void emit_block(ELds& L, uint32_t* s_fast, const Args
     ss.status = PBL_UNSUPPORTED;
     if (staged) {
       wave_sync();
-      slow_walk_t<SlowLds, PBL_RW_VALU>(SlowLds{V}, blen, flags, seq, to_lds_ptr(reinterpret_cast<uint8_t*>(&L.sl)),
+      slow_walk_t<LdsBlk, PBL_RW_VALU>(LdsBlk{V}, blen, flags, seq, to_lds_ptr(reinterpret_cast<uint8_t*>(&L.sl)),
                                         uint32_t(sizeof(L.sl)), kPassAll, O, b, excl, &ss);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       wave_sync();  // (the stage may become the key buffer below)
       PSTAMP(A, b, 3, l == 0);
     }
     if (ss.status == PBL_UNSUPPORTED)
-      slow_walk_t<SlowGlb, PBL_BIG_U>(SlowGlb{to_glb(g), blen}, blen, flags, seq,
+      slow_walk_t<GlbBlk, PBL_BIG_U>(GlbBlk{to_glb(g), blen}, blen, flags, seq,
                                       to_lds_ptr(reinterpret_cast<uint8_t*>(L.st.x)), uint32_t(sizeof(L.st)),
                                       kPassAll, O, b, excl, &ss);
     PSTAMP(A, b, 4, l == 0);
@@ -580,3 +563,5 @@ __global__ void __launch_bounds__(kRwWaves * kWave) row_wave_emit_kernel(Args A)
 }
 
 }  // namespace rwave
+}  // namespace row
+}  // namespace pbl

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "common.hip.h"
+#include "rowblk_core.hip.h"
 
 namespace pbl {
 namespace tf {
@@ -34,8 +35,6 @@ constexpr uint32_t kTfTile = 1024;  // blocks per scan tile (256 threads x 4)
 __host__ __device__ inline uint64_t tf_tiles(uint32_t nb) { return (uint64_t(nb) + kTfTile - 1) / kTfTile; }
 __host__ __device__ inline uint64_t tf_lb_bytes(uint32_t nb) { return 80ull * tf_tiles(nb); }
 __host__ __device__ inline uint64_t tf_cnt_offset(uint32_t nb) { return kTfWs + tf_lb_bytes(nb); }
-constexpr uint64_t kTfMask = ((1ull << 56) - 1) << 8 | 191u;  // TrailerObsoleteMask (rowblk_writer.go:30-42)
-constexpr uint64_t kTfInvalid = 191u;                          // InternalKeyKindInvalid
 
 struct TfArgs {
   pbl_decode_out in, out;
@@ -68,16 +67,16 @@ __device__ inline uint32_t split_len(const FKey& k, uint32_t split) {
   return n;  // base.DefaultSplit: the whole key
 }
 
-// uint32 varint of rowblk_iter.go:2020-2038 (5th byte << 28); returns bytes read
-__device__ inline uint32_t tf_varint(gptr<const uint8_t> p, uint32_t* v) {
-  uint32_t r = 0;
-  for (uint32_t i = 0; i < 5; i++) {
-    const uint32_t b = p[i];
-    if (i == 4) { *v = r | (b << 28); return 5; }
-    r |= (b & 0x7fu) << (7 * i);
-    if (b < 128) { *v = r; return i + 1; }
-  }
-  return 5;
+// Header length of the row entry at block offset e (row::varint_at's rules).
+// The decode accepted the entry, so no varint runs past the block: each may
+// read its 5 bytes.
+__device__ __forceinline__ uint32_t entry_hdr(gptr<const uint8_t> blk, uint32_t e, uint32_t* s, uint32_t* u,
+                                              uint32_t* vl) {
+  const auto from = [blk](uint32_t p) { return [q = blk + p](uint32_t i) { return uint32_t(q[i]); }; };
+  uint32_t h = row::varint_at(from(e), 5u, s);
+  h += row::varint_at(from(e + h), 5u, u);
+  h += row::varint_at(from(e + h), 5u, vl);
+  return h;
 }
 
 // The raw internal key (< 8 bytes, byte i at bits 8i) of row entry j, an entry
@@ -91,9 +90,7 @@ __device__ inline uint64_t raw_short_key(const TfArgs& A, gptr<const uint8_t> bl
   const pbl_decode_out& I = A.in;
   uint32_t s, u, vl;
   uint32_t e = to_glb(I.entry_off)[kv0 + j];
-  uint32_t h = tf_varint(blk + e, &s);
-  h += tf_varint(blk + e + h, &u);
-  h += tf_varint(blk + e + h, &vl);
+  uint32_t h = entry_hdr(blk, e, &s, &u, &vl);
   const uint32_t kl = s + u;
   *kl_out = kl;
   uint64_t raw = 0;
@@ -115,9 +112,7 @@ __device__ inline uint64_t raw_short_key(const TfArgs& A, gptr<const uint8_t> bl
       break;
     }
     e = to_glb(I.entry_off)[kv0 + k];
-    h = tf_varint(blk + e, &ks);
-    h += tf_varint(blk + e + h, &u);
-    h += tf_varint(blk + e + h, &vl);
+    h = entry_hdr(blk, e, &ks, &u, &vl);
     kkl = ks + u;
   }
   return raw;
@@ -163,20 +158,23 @@ __device__ inline KvView kv_view(const TfArgs& A, uint32_t b, uint64_t kv0, uint
       uint64_t raw = rk << (8 * (8 - kl));
       for (uint32_t i = 0; i < 8 - kl; i++) raw |= uint64_t(to_glb(T.prefix)[ukl + i]) << (8 * i);
       v.valid = true;
-      v.fl = uint8_t((v.fl & ~PBL_KV_INVALID_KEY) | ((raw & 64u) ? PBL_KV_OBSOLETE : 0u));
-      v.vis = !(T.hide_obsolete_points && (raw & 64u));
-      v.tr = raw & kTfMask;
+      uint32_t fl = v.fl & ~uint32_t(PBL_KV_INVALID_KEY);
+      uint64_t ukl64;  // (= ukl)
+      row::split_trailer(raw, uint64_t(T.prefix_len) + kl, 0u, &v.tr, &ukl64, &fl);
+      v.vis = !(T.hide_obsolete_points && (fl & PBL_KV_OBSOLETE));
       v.F.fp = ukl;
       v.F.kn = 0;
       if ((A.src.flags & PBL_ROW_VALUE_PREFIX) && (v.tr & 0xffu) == 1u) {  // kind SET: the value prefix
         if (v.vlen == 0) {
           v.corrupt = v.vis;  // Go: i.val[0] panics (only reached for a visible point)
         } else {
-          const uint32_t pre = to_glb(I.val_bytes)[vb_in + v.vo];
-          if ((pre & 0xC0u) == 0 || (A.src.flags & PBL_ROW_NO_VALUER)) { v.vo++; v.vlen--; }
-          else v.fl |= (pre & 0xC0u) == 0x80u ? PBL_KV_VALBLK_HANDLE : PBL_KV_BLOB_HANDLE;
+          uint32_t skip;
+          row::value_prefix(to_glb(I.val_bytes)[vb_in + v.vo], A.src.flags, &skip, &fl);
+          v.vo += skip;
+          v.vlen -= skip;
         }
       }
+      v.fl = uint8_t(fl);
     }
   }
   if (!v.valid) {

@@ -30,3 +30,51 @@ def mvcc_block(rng: random.Random, n: int = 200, ri: int = 16, vp: bool = False,
                 w.add_with_optional_value_prefix(uk, tr, obs, val, msk, False, 0, False)
             i += 1
     return w.finish()
+
+
+def header_cases(lead_value_len: int = 0):
+    """Blocks for what a shared varint / entry-header decoder could get wrong:
+    [(name, block)], each block written by the row writer with raw keys and
+    then patched in its entries' 3-byte headers.  Every key shares nothing with
+    the entry before the case's first, so entry i of a case has the header
+    [shared, unshared, value length] in single bytes at its offset.
+    lead_value_len > 0 puts one entry with a value of that length first (a
+    block past the 32 KiB LDS stage takes the big-block passes); at most 4
+    entries per block either way."""
+    def ik(user, kind=2, seq=5):
+        return user + make_trailer(seq, kind).to_bytes(8, "little")
+
+    lead = [(ik(b"AAAAAAAA"), b"L" * lead_value_len)] if lead_value_len else []
+
+    def block(entries):
+        w = Writer(16)  # (one restart, at offset 0: patches that move entries leave the table valid)
+        for k, v in lead + entries:
+            w.add_raw(k, v)
+        return w.finish()
+
+    def build(entries, patches=()):
+        # entry i's offset: the length of the block that ends before it, less its 8-byte restart table
+        offs = [len(block(entries[:i])) - 8 for i in range(len(entries))]
+        b = bytearray(block(entries))
+        for i, k, new in sorted(patches, reverse=True):
+            b[offs[i] + k: offs[i] + k + 1] = new
+        return bytes(b), offs
+
+    two = [(ik(b"bbbbbbbb"), b"v" * 10), (ik(b"bbbbbbbc", 1), b"\x80hnd")]
+    same = [(ik(b"bbbbbbbb"), b"val"), (ik(b"bbbbbbbb"), b"")]  # the second: [16, 0, 0]
+    cases = [
+        ("vlen 3 bytes", build(two, [(0, 2, b"\x8a\x80\x00")])),
+        ("vlen 4 bytes", build(two, [(0, 2, b"\x8a\x80\x80\x00")])),
+        ("vlen 5 bytes, high bits in the last", build(two, [(0, 2, b"\x8a\x80\x80\x80\xf0")])),
+        ("unshared as a 2-byte 16", build(two, [(0, 1, b"\x90\x00")])),
+        ("header ends at the restart table", build(same)),
+        ("header runs into the restart table", build(same, [(1, 2, b"\x80")])),
+        ("first entry shared != 0", build(two, [(0, 0, b"\x01")])),
+        ("shared > previous key", build([(ik(b"bb"), b"v"), (ik(b"bbc"), b"w")], [(1, 0, b"\x28")])),
+        ("SET with an empty value", build([(ik(b"bbbbbbba", 1), b"\x00abc"), (ik(b"bbbbbbbb", 1), b"")])),
+        ("key shorter than 8 bytes", build([(ik(b"bbbbbbbb"), b"v"), (b"bcd", b"val")])),
+        ("vlen 3 bytes, canonical (20000)", build([(ik(b"bbbbbbbb"), b"v" * 20000), (ik(b"bbbbbbbc", 1), b"\x80hnd")])),
+    ]
+    blk, offs = cases[4][1]
+    assert offs[1] + 3 == len(blk) - 8, "the last header byte sits right before the restart table"
+    return [(name, b) for name, (b, _) in cases]

@@ -183,3 +183,22 @@ def test_generator_blocks_decode_on_oracle():
     per = np.diff(r["blk_kv_base"].astype(np.int64))
     assert 250 <= per.min() and per.max() <= 290
     assert (np.diff(r["blk_rst_base"].astype(np.int64)) >= 16).all()
+
+
+def test_header_cases_are_not_vacuous():
+    """The varint / entry-header matrix of tests/test_row_kernels_gpu.py
+    (rowutil.header_cases) holds decodable and corrupt blocks alike: at least
+    three cases decode, and the others report at least two distinct statuses."""
+    from rowutil import header_cases
+    from test_rowblk_gpu import pack
+    cases = header_cases()
+    assert len(cases) < 20
+    o = oracle.rowblk_decode_batch(*pack([b for _, b in cases]), N.PBL_ROW_VALUE_PREFIX)
+    st = [int(s) for s in o["blk_status"]]
+    assert sum(s == N.PBL_OK for s in st) >= 3, st
+    assert len({s for s in st if s != N.PBL_OK}) >= 2, st
+    # behind a 33 KiB value (the big-block passes) the blocks still do both
+    big = header_cases(33 * 1024)
+    assert all(32768 < len(b) for _, b in big)
+    ob = oracle.rowblk_decode_batch(*pack([b for _, b in big]), N.PBL_ROW_VALUE_PREFIX)
+    assert N.PBL_OK in ob["blk_status"] and N.PBL_CORRUPT_BOUNDS in ob["blk_status"]

@@ -196,3 +196,47 @@ def test_overflow_and_size_pass(kern):
         (h["n_kv"], h["key_bytes_total"], h["val_bytes_total"], h["n_restarts"], 0)
     assert np.array_equal(s.blk_kv_base.cpu().numpy(), h["blk_kv_base"])
     assert np.array_equal(s.blk_val_base.cpu().numpy(), h["blk_val_base"])
+
+
+HEADER_PATHS = {
+    # path: (blocks behind a 33 KiB value, batch flags)
+    "pool": (False, N.PBL_KERNEL_POOL | N.PBL_ROW_VALUE_PREFIX),
+    "wave": (False, N.PBL_BATCH_VARLEN),  # (value prefixes would route the batch to the pool kernel)
+    "big": (True, N.PBL_KERNEL_POOL | N.PBL_ROW_VALUE_PREFIX),
+    "big-wave": (True, N.PBL_BATCH_VARLEN),
+}
+
+
+@pytest.mark.parametrize("path", sorted(HEADER_PATHS))
+def test_header_cases(path):
+    """What one shared varint / entry-header decoder could get wrong
+    (rowutil.header_cases: 3-, 4- and 5-byte value lengths, a non-canonical
+    2-byte varint, a header ending at or running into the restart table, a first
+    entry with shared != 0, shared past the previous key, a SET without its
+    value prefix byte, a key shorter than 8 bytes), on the staging-pool kernel,
+    the two-pass form and, behind a 33 KiB value, the big-block passes: statuses
+    and every array equal the oracle's.  (That the cases hold decodable and
+    corrupt blocks: tests/test_oracle_rowblk.py::test_header_cases_are_not_vacuous.)"""
+    from rowutil import header_cases
+    big, flags = HEADER_PATHS[path]
+    cases = header_cases(33 * 1024 if big else 0)
+    kern = flags & (N.PBL_KERNEL_POOL | N.PBL_BATCH_VARLEN)
+    check(*pack([b for _, b in cases]), flags & ~kern, f"header cases {path}", kern)
+
+
+@pytest.mark.parametrize("split,suffix", [(N.PBL_SPLIT_TESTKEYS, b"@9"), (N.PBL_SPLIT_CRDB, b"\x00" * 7 + b"\x07\x09")])
+def test_header_cases_transform_reparse(split, suffix):
+    """The header cases that decode, through the device transforms with a
+    synthetic prefix and suffix: the short key becomes valid under the prefix,
+    which re-reads its entry header (and its neighbours') from the block."""
+    from rowutil import header_cases
+    from test_transforms_gpu import Transforms, run
+    flags = N.PBL_ROW_VALUE_PREFIX
+    cases = header_cases()
+    st = oracle.rowblk_decode_batch(*pack([b for _, b in cases]), flags)["blk_status"]
+    blocks = [b for (_, b), s in zip(cases, st) if s == N.PBL_OK]
+    assert len(blocks) >= 3
+    t = Transforms(synthetic_prefix=b"PQR\x02\x02\x00\x00\x00", synthetic_suffix=suffix, split=split)
+    g, o = run(*pack(blocks), N.PBL_FMT_ROW, t, flags=flags)
+    assert_same(g, o, f"header cases, transforms split={split}")
+    assert not (g["kv_flags"] & N.PBL_KV_INVALID_KEY).any()

@@ -46,7 +46,7 @@ def test_reference_v8_blocks():
     with open(GOLDEN) as f:
         cases = json.load(f)["tiering"]["blocks"]
     blocks = [bytes.fromhex(c["block"]) for c in cases]
-    for flags in (T, 0, T | N.PBL_KERNEL_SINGLE, T | N.PBL_ROW_HIDE_OBSOLETE):
+    for flags in (T, 0, T | N.PBL_KERNEL_SINGLE, T | N.PBL_KERNEL_PIPE, T | N.PBL_ROW_HIDE_OBSOLETE):
         g = check(*pack(blocks), SCHEMA_DEFAULT, flags, ctx=f"golden v8 flags={flags:#x}")
         want = [(r["span"], r["attr"]) if flags & T else (0, 0) for c in cases for r in c["rows"]]
         assert list(zip(g["tiering_span_id"].tolist(), g["tiering_attr"].tolist())) == want
@@ -62,7 +62,7 @@ def test_random_v8_blocks(schema):
         blk, _, _ = build_block_meta(schema, rows, random_metas(rng, len(rows)), rng.choice([1, 16, 64]))
         blocks.append(blk)
     buf, off, lens = pack(blocks)
-    for flags in (T, T | N.PBL_KERNEL_SINGLE, T | N.PBL_ROW_HIDE_OBSOLETE, T | N.PBL_BATCH_VARLEN):
+    for flags in (T, T | N.PBL_KERNEL_SINGLE, T | N.PBL_KERNEL_PIPE, T | N.PBL_ROW_HIDE_OBSOLETE, T | N.PBL_BATCH_VARLEN):
         check(buf, off, lens, schema, flags, ctx=f"random v8 schema={schema} flags={flags:#x}")
 
 
@@ -90,7 +90,7 @@ def test_corrupt_tiering_columns():
             blk[h] = rng.choice([1, 3])  # a tiering column of the wrong type
         blocks.append(bytes(blk))
     buf, off, lens = pack(blocks)
-    for flags in (T, T | N.PBL_KERNEL_SINGLE, T | N.PBL_ROW_HIDE_OBSOLETE):
+    for flags in (T, T | N.PBL_KERNEL_SINGLE, T | N.PBL_KERNEL_PIPE, T | N.PBL_ROW_HIDE_OBSOLETE):
         g = check(buf, off, lens, SCHEMA_DEFAULT, flags, ctx=f"corrupt v8 flags={flags:#x}")
         assert g["status_mask"] & (1 << N.PBL_CORRUPT_COLBLK_HEADER)
 
