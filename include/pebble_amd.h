@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define PBL_ABI_VERSION 8
+#define PBL_ABI_VERSION 9
 
 /* ---- status codes (per block, and OR-ed as bit masks into totals) ---------- */
 enum {
@@ -49,7 +49,12 @@ enum {
   PBL_CORRUPT_FIRST_KEY = 2,     /* rowblk_iter.go:429-434,471-476 */
   PBL_CORRUPT_BOUNDS = 3,        /* entry/column extends past the block */
   PBL_CORRUPT_COLBLK_HEADER = 4, /* data_block.go:1005-1009 (panic -> corruption) */
-  PBL_UNSUPPORTED = 5,           /* legal but outside this build's limits */
+  PBL_UNSUPPORTED = 5,           /* legal but outside this build's limits.  For a
+                                    row block: a key longer than 32768 bytes with no
+                                    (or too small a) key spill slot in the workspace
+                                    (pbl_workspace_bytes_for), or more than 4 GiB of
+                                    key or value bytes in one block.  The block is
+                                    not corrupt: decode it on the host. */
   PBL_OVERFLOW = 6,              /* an output capacity was too small: nothing written */
   PBL_INVALID_ARG = 7,
   PBL_DEVICE_ERROR = 8,
@@ -160,7 +165,10 @@ typedef struct pbl_block_batch {
   const uint32_t* block_len; /* [n_blocks] byte length of each block (< 4 GiB: the
                                 rowblk 64-bit offsets of rowblk_64bit_test.go:28-183
                                 are out of scope; blocks are <= 32 KiB in practice
-                                and the general path handles any u32 length)      */
+                                and the general path handles any u32 length; a
+                                row key past 32768 bytes, which only a longer
+                                block can hold, needs the workspace of
+                                pbl_workspace_bytes_for)                          */
   uint32_t n_blocks;
   uint32_t format;           /* PBL_FMT_* for every block of the batch              */
   uint32_t flags;            /* PBL_ROW_* flags                                     */
@@ -215,7 +223,9 @@ typedef struct pbl_decode_out {
   uint32_t* blk_status;   /* [n_blocks] PBL_* status per block                    */
   pbl_totals* totals;     /* [1]                                                  */
   uint64_t kv_cap, key_cap, val_cap, rst_cap;
-  void* workspace;        /* device scratch of pbl_workspace_bytes(n_blocks) bytes */
+  void* workspace;        /* device scratch of pbl_workspace_bytes(n_blocks) bytes,
+                             or of pbl_workspace_bytes_for(n_blocks, longest block);
+                             16-byte aligned */
   uint64_t workspace_bytes;
   uint64_t* tiering_span_id; /* [kv_cap] (optional) base.KVMeta.TieringSpanID per KV   */
   uint64_t* tiering_attr;    /* [kv_cap] (optional) base.KVMeta.TieringAttribute per KV;
@@ -227,6 +237,30 @@ int pbl_abi_version(void);
 
 /* Device scratch the decode needs for a batch of n_blocks (look-back state). */
 uint64_t pbl_workspace_bytes(uint32_t n_blocks);
+
+/*
+ * Row keys longer than 32768 bytes (ABI v9).  The general row walk keeps the
+ * current key in a 32 KiB LDS buffer; Go's readEntry grows fullKey without
+ * bound (rowblk_iter.go:400-403).  With a workspace of pbl_workspace_bytes(n)
+ * a row block holding a longer key reports PBL_UNSUPPORTED (every other block
+ * of the batch is unaffected).  pbl_workspace_bytes_for lifts the limit: for
+ * max_block_len <= 32768 (no block can hold such a key: a key is never longer
+ * than its block) it returns pbl_workspace_bytes(n_blocks); otherwise it adds,
+ * after the existing layout (whose size and offsets are unchanged; no further
+ * id list is needed), PBL_LONGKEY_WGS key spill slots of max_block_len rounded
+ * up to 16 bytes each.  Pass the longest block.Handle length of the batch; the
+ * lengths are known on the host.  The decode takes the slot size from
+ * out->workspace_bytes: (workspace_bytes - pbl_workspace_bytes(n)) /
+ * PBL_LONGKEY_WGS rounded down to 16, so a smaller surplus gives smaller slots,
+ * and a key that outgrows its slot (more than 32768 - 48 + slot bytes) reports
+ * PBL_UNSUPPORTED.  Such blocks are sized and written by PBL_LONGKEY_WGS
+ * one-wave workgroups, each looping over the listed blocks with its own slot:
+ * a cold path, stream-ordered like the rest; the host reads nothing back.
+ */
+#ifndef PBL_LONGKEY_WGS
+#define PBL_LONGKEY_WGS 32
+#endif
+uint64_t pbl_workspace_bytes_for(uint32_t n_blocks, uint32_t max_block_len);
 
 /*
  * Decode every block of `batch` into `out` on `stream`: one stream-ordered

@@ -42,7 +42,8 @@ PBL_TABLE_PEBBLEV5, PBL_TABLE_PEBBLEV6, PBL_TABLE_PEBBLEV7 = 7, 8, 9
 PBL_CHECKSUM_NONE, PBL_CHECKSUM_CRC32C, PBL_CHECKSUM_XXHASH, PBL_CHECKSUM_XXHASH64 = 0, 1, 2, 3
 PBL_COMPRESSION_NONE, PBL_COMPRESSION_SNAPPY, PBL_COMPRESSION_ZSTD, PBL_COMPRESSION_MINLZ = 0, 1, 7, 8
 
-ABI_VERSION = 8  # include/pebble_amd.h PBL_ABI_VERSION
+ABI_VERSION = 9  # include/pebble_amd.h PBL_ABI_VERSION
+PBL_LONGKEY_WGS = 32  # key spill slots of pbl_workspace_bytes_for
 
 PBL_FMT_ROW = 0
 PBL_FMT_COL_DEFAULT = 1
@@ -208,6 +209,7 @@ SIGNATURES = {
     "pbl_key_split": (ctypes.c_uint64, [ctypes.c_uint32, _u8p, ctypes.c_uint64]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
     "pbl_decode_batch": (ctypes.c_int, [ctypes.POINTER(BlockBatchC), ctypes.POINTER(DecodeOutC), _vp]),
     "pbl_size_batch": (ctypes.c_int, [ctypes.POINTER(BlockBatchC), ctypes.POINTER(DecodeOutC), _vp]),
     "pbl_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),

@@ -91,6 +91,8 @@ class BlockBatch:
     flags: int = 0
     block_format: Optional[torch.Tensor] = None  # uint8 [n] per-block PBL_FMT_* (mixed batches)
     synthetic_seq_num: int = 0  # blockiter.SyntheticSeqNum fused into the decode (0 = unset)
+    max_block_len: int = 0      # the longest block (from_host records it; 0 = unknown): sizes the
+                                # workspace's key spill slots (pbl_workspace_bytes_for)
 
     @property
     def n_blocks(self) -> int:
@@ -114,7 +116,7 @@ class BlockBatch:
         bf = None
         if block_format is not None:
             bf = torch.from_numpy(np.ascontiguousarray(block_format, dtype=np.uint8)).to(device)
-        return cls(b, o, l, fmt, flags, bf)
+        return cls(b, o, l, fmt, flags, bf, max_block_len=int(np.max(lens)) if len(lens) else 0)
 
     @classmethod
     def from_blocks(cls, blocks: list, device="cuda", fmt: int = N.PBL_FMT_ROW, flags: int = 0,
@@ -185,11 +187,16 @@ class DecodedBatch:
 
     @classmethod
     def allocate(cls, n_blocks: int, cap: Capacity, device, entry_off: bool = True,
-                 restarts: bool = True, meta: bool = False) -> "DecodedBatch":
+                 restarts: bool = True, meta: bool = False, max_block_len: int = 0) -> "DecodedBatch":
+        """`max_block_len`: the batch's longest block; past 32 KiB the workspace
+        also holds the key spill slots that row keys longer than 32 KiB need
+        (pbl_workspace_bytes_for).  0: the workspace of pbl_workspace_bytes,
+        with which such a block reports PBL_UNSUPPORTED."""
         d = torch.device(device)
         u = lambda n, dt: torch.empty(max(int(n), 1), dtype=dt, device=d)  # noqa: E731
         lib = N.lib()
-        ws = int(lib.pbl_workspace_bytes(n_blocks))
+        ws_for = getattr(lib, "pbl_workspace_bytes_for", None)  # (absent from an older A/B build, PBL_LIB)
+        ws = int(ws_for(n_blocks, max_block_len) if max_block_len and ws_for else lib.pbl_workspace_bytes(n_blocks))
         return cls(
             n_blocks=n_blocks,
             trailer=u(cap.kv, torch.int64), kv_flags=u(cap.kv, torch.uint8),
@@ -269,7 +276,8 @@ def size_batch(batch: BlockBatch, stream=None) -> DecodedBatch:
     in a DecodedBatch whose per-KV arrays are empty (Capacity 0)."""
     st = stream if stream is not None else torch.cuda.current_stream(batch.device)
     with torch.cuda.stream(st):
-        out = DecodedBatch.allocate(batch.n_blocks, Capacity(0, 0, 0, 0), batch.device)
+        out = DecodedBatch.allocate(batch.n_blocks, Capacity(0, 0, 0, 0), batch.device,
+                                    max_block_len=batch.max_block_len)
     b = batch.c_struct()
     o = out.c_struct()
     rc = N.lib().pbl_size_batch(ctypes.byref(b), ctypes.byref(o), ctypes.c_void_p(st.cuda_stream))
@@ -294,7 +302,8 @@ def decode(batch: BlockBatch, cap: Optional[Capacity] = None, stream=None, entry
         cap = Capacity(kv=int(t.n_kv), key=int(t.key_bytes), val=int(t.val_bytes), rst=int(t.n_restarts))
     cap = cap or Capacity.estimate(batch)
     with torch.cuda.stream(st):
-        out = DecodedBatch.allocate(batch.n_blocks, cap, batch.device, entry_off, restarts, meta)
+        out = DecodedBatch.allocate(batch.n_blocks, cap, batch.device, entry_off, restarts, meta,
+                                    batch.max_block_len)
     decode_into(batch, out, st)
     out.source = batch
     st.synchronize()
@@ -303,7 +312,8 @@ def decode(batch: BlockBatch, cap: Optional[Capacity] = None, stream=None, entry
         cap = Capacity(kv=int(t.n_kv) + 1, key=int(t.key_bytes) + 1, val=int(t.val_bytes) + 1,
                        rst=int(t.n_restarts) + 1)
         with torch.cuda.stream(st):
-            out = DecodedBatch.allocate(batch.n_blocks, cap, batch.device, entry_off, restarts, meta)
+            out = DecodedBatch.allocate(batch.n_blocks, cap, batch.device, entry_off, restarts, meta,
+                                        batch.max_block_len)
         decode_into(batch, out, st)
         out.source = batch
         st.synchronize()

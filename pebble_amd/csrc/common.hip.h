@@ -109,6 +109,15 @@ __host__ __device__ inline uint64_t ws_ent_offset(uint32_t n_blocks) {
 __host__ __device__ inline uint64_t ws_alloc_bytes(uint32_t n_blocks) {
   return ws_ent_offset(n_blocks) + 2ull * kEntRec * n_blocks;
 }
+// Past all of that, when the caller sized the workspace with
+// pbl_workspace_bytes_for: the key spill slots of the long-key kernels
+// (rowblk_long.hip.h), one per workgroup, 16-B aligned.  Their size is what the
+// caller's workspace leaves: 0 for one sized by pbl_workspace_bytes.
+constexpr uint32_t kLongKeyWgs = PBL_LONGKEY_WGS;
+__host__ __device__ inline uint64_t ws_spill_slot_bytes(uint64_t workspace_bytes, uint32_t n_blocks) {
+  const uint64_t a = ws_alloc_bytes(n_blocks);
+  return workspace_bytes > a ? ((workspace_bytes - a) / kLongKeyWgs) & ~uint64_t(15) : 0;
+}
 
 
 // Address-space-typed pointers.  A generic pointer compiles to FLAT

@@ -23,6 +23,7 @@ namespace rowc {
 constexpr uint32_t kBigKeySmall = PBL_BIG_KEYBUF;  // the sizes tier-1 key buffer
 constexpr int kWsBigRedo = 5;  // header u32 [5]: sizes tier-2 blocks (their ids in the redo area, ws_redo_offset)
 constexpr int kWsBigPend = 6;  // header u32 [6]: blocks the row kernel did not write (ids at ws_pend_offset)
+constexpr int kWsBigLong = 7;  // header u32 [7]: a key past the 32 KiB buffer (rowblk_long.hip.h)
 
 // Size pass for the blocks past the LDS stage (blen > kMaxFastLen), launched
 // ahead of the row kernel on the same stream.  Their count walk reads global
@@ -54,8 +55,9 @@ __device__ __forceinline__ void big_block_publish(const Args& A, uint32_t b, con
 // The count walk of a big block; a block failing Iter.Init's checks (zero
 // restarts, a restart table past the block, a bad first entry) gets that
 // status and a zero aggregate, which big_block_publish publishes like any other.
+template <bool kSpill = false>
 __device__ __forceinline__ void big_block_count(const Args& A, uint32_t b, lptr<uint8_t> keybuf, uint32_t keycap,
-                                                SlowState* ss) {
+                                                SlowState* ss, gptr<uint8_t> spill = nullptr, uint64_t spillcap = 0) {
   const uint32_t blen = A.in.block_len[b];
   const uint8_t* gblk = A.in.blocks + A.in.block_off[b];
   uint32_t roff, nres;
@@ -66,8 +68,8 @@ __device__ __forceinline__ void big_block_count(const Args& A, uint32_t b, lptr<
     return;
   }
   const uint64_t dummy[kNumComp] = {0, 0, 0, 0};
-  slow_walk_t<GlbBlk, 1>(GlbBlk{to_glb(gblk), blen}, blen, A.in.flags, A.in.synthetic_seq_num, keybuf, keycap, kPassCount,
-                          A.out, b, dummy, ss);
+  slow_walk_t<GlbBlk, 1, kSpill>(GlbBlk{to_glb(gblk), blen}, blen, A.in.flags, A.in.synthetic_seq_num, keybuf, keycap,
+                                  kPassCount, A.out, b, dummy, ss, spill, spillcap);
 }
 
 __global__ void __launch_bounds__(kWave) big_block_sizes_kernel(Args A) {
@@ -94,8 +96,19 @@ __global__ void __launch_bounds__(kWave) big_block_sizes_kernel(Args A) {
   }
 }
 
-__global__ void __launch_bounds__(kWave) big_block_sizes2_kernel(Args A) {
-  __shared__ uint4 keybuf4[kLdsBlkBytes / 16];
+// Tier 2's body.  kList (long_key_sizes2_kernel in rowblk_long.hip.h, launched
+// in its place for a workspace with key spill slots): a block whose walk
+// stopped at a key past the 32 KiB buffer is listed for tier 3 instead of
+// published (ids at ws_ent_offset, which the pool path leaves unused; their
+// count at header word kWsBigLong).  A block whose totals pass 4 GiB stays
+// PBL_UNSUPPORTED.  The two are told apart by the sums at the point where the
+// walk stopped: a block whose sums had already passed 4 GiB when it met the
+// long key is published as PBL_UNSUPPORTED without tier 3, which is its final
+// status unless a later entry is corrupt (the oracle would then report
+// PBL_CORRUPT_BOUNDS); that needs more than 4 GiB of decoded keys or values
+// ahead of a long key in one block, which no table holds.
+template <bool kList>
+__device__ __forceinline__ void big_block_sizes2_body(const Args& A, uint4* keybuf4) {
   const uint32_t nb = A.in.n_blocks;
   const uint32_t* hdr = reinterpret_cast<const uint32_t*>(A.out.workspace);
   const uint32_t n = __hip_atomic_load(to_glb(hdr) + kWsBigRedo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -105,8 +118,20 @@ __global__ void __launch_bounds__(kWave) big_block_sizes2_kernel(Args A) {
     const uint32_t b = to_glb(redo)[i];
     SlowState ss;
     big_block_count(A, b, to_lds_ptr(reinterpret_cast<uint8_t*>(keybuf4)), uint32_t(kLdsBlkBytes), &ss);
+    if constexpr (kList) {
+      if (ss.status == PBL_UNSUPPORTED && !((ss.kb | ss.vb) >> 32)) {
+        uint32_t* lng = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(A.out.workspace) + ws_ent_offset(nb));
+        if (lane_id() == 0) to_glb(lng)[g_atomic_add(const_cast<uint32_t*>(hdr) + kWsBigLong, 1u)] = b;
+        continue;
+      }
+    }
     big_block_publish(A, b, ss);
   }
+}
+
+__global__ void __launch_bounds__(kWave) big_block_sizes2_kernel(Args A) {
+  __shared__ uint4 keybuf4[kLdsBlkBytes / 16];
+  big_block_sizes2_body<false>(A, keybuf4);
 }
 
 // Outputs of the blocks past the LDS stage.  The row kernel walks each one

@@ -6,6 +6,8 @@
 // Kernels:
 //   rowblk_pool_kernel   (rowblk_pool.hip.h) the staging-pool kernel
 //   big_block_*_kernel   (rowblk_big.hip.h) blocks past the 32 KiB LDS stage
+//   long_key_*_kernel    (rowblk_long.hip.h) their blocks with a key past the 32
+//                        KiB key buffer, the key spilled to a workspace slot
 //   row_wave_*_kernel    (rowblk_wave.hip.h) PBL_BATCH_VARLEN batches in two
 //                        passes (sizes, bases_scan_kernel<true>, outputs)
 //   mixed_*              row + colblk batches (config 4): the ids split by
@@ -224,18 +226,42 @@ uint64_t persistent_grid(hipStream_t st, PersistentKernel k, const void* fn, uin
 
 }  // namespace pbl
 
+// (after every other kernel of this file: the code of the kernels that every
+// launch runs sits where it did before these were added)
+#include "rowblk_long.hip.h"
+
 namespace {
 // The big row blocks' passes (rowblk_big.hip.h): sizes before the row kernel
 // (tier 1 a workgroup per PBL_BIG_WIN-block window, tier 2 over the blocks it
 // listed); after it, the outputs of the blocks the row kernel did not write.
+// The long-key kernels (a key past the 32 KiB buffer, spilled to a workspace
+// slot) follow each of them, when the caller's workspace holds slots
+// (pbl_workspace_bytes_for): sizes tier 3 over the blocks tier 2 listed, and
+// after the values pass the outputs of those blocks.
+bool has_spill_slots(const pbl::Args& a) {
+  return pbl::ws_spill_slot_bytes(a.out.workspace_bytes, a.in.n_blocks) != 0;
+}
+
 void launch_big_sizes(const pbl::Args& a, hipStream_t st, uint32_t small) {
   const uint32_t g1 = (a.in.n_blocks + PBL_BIG_WIN - 1) / PBL_BIG_WIN;
   hipLaunchKernelGGL(pbl::row::rowc::big_block_sizes_kernel, dim3(g1), dim3(pbl::kWave), 0, st, a);
-  hipLaunchKernelGGL(pbl::row::rowc::big_block_sizes2_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
+  if (!has_spill_slots(a)) {
+    hipLaunchKernelGGL(pbl::row::rowc::big_block_sizes2_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
+    return;
+  }
+  hipLaunchKernelGGL(pbl::row::rowc::long_key_sizes2_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
+  hipLaunchKernelGGL(pbl::row::rowc::long_key_sizes_kernel, dim3(pbl::kLongKeyWgs), dim3(pbl::kWave), 0, st, a);
+}
+
+void launch_long_values(const pbl::Args& a, hipStream_t st, uint64_t list_off, int count_word) {
+  if (has_spill_slots(a))
+    hipLaunchKernelGGL(pbl::row::rowc::long_key_values_kernel, dim3(pbl::kLongKeyWgs), dim3(pbl::kWave), 0, st, a,
+                       list_off, count_word);
 }
 
 void launch_big_values(const pbl::Args& a, hipStream_t st, uint32_t small) {
   hipLaunchKernelGGL(pbl::row::rowc::big_block_values_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
+  launch_long_values(a, st, pbl::ws_ent_offset(a.in.n_blocks), pbl::row::rowc::kWsBigLong);
 }
 
 // The staging-pool kernel (rowblk_pool.hip.h): its persistent grid, and its
@@ -330,14 +356,20 @@ int launch_row_wave(const pbl::Args& a, hipStream_t st) {
     return PBL_DEVICE_ERROR;
   namespace cw = pbl::col::cwave;
   const uint32_t nt = (nb + cw::kScanTile - 1) / cw::kScanTile;
-  hipLaunchKernelGGL(pbl::row::rwave::row_wave_size_kernel, dim3((nb + pbl::kWave - 1) / pbl::kWave),
-                     dim3(pbl::kWave), 0, st, a);
-  hipLaunchKernelGGL(pbl::row::rwave::row_wave_dense_kernel, dim3(std::min<uint32_t>(nb, uint32_t(cus) * 8)),
-                     dim3(pbl::kWave), 0, st, a);
-  hipLaunchKernelGGL(cw::bases_scan_kernel<true>, dim3(std::min<uint32_t>(nt, uint32_t(cus) * 2)), dim3(pbl::kTPB), 0,
-                     st, a);
-  hipLaunchKernelGGL(pbl::row::rwave::row_wave_emit_kernel, dim3(nb), dim3(pbl::row::rwave::kRwWaves * pbl::kWave), 0,
-                     st, a);
+  // (a workspace with key spill slots: the kernels' long-key forms)
+  pbl::with_bool(has_spill_slots(a), [&](auto lk) {
+    constexpr bool kLong = decltype(lk)::value;
+    hipLaunchKernelGGL(pbl::row::rwave::row_wave_size_kernel<kLong>, dim3((nb + pbl::kWave - 1) / pbl::kWave),
+                       dim3(pbl::kWave), 0, st, a);
+    hipLaunchKernelGGL(pbl::row::rwave::row_wave_dense_kernel<kLong>, dim3(std::min<uint32_t>(nb, uint32_t(cus) * 8)),
+                       dim3(pbl::kWave), 0, st, a);
+    hipLaunchKernelGGL(cw::bases_scan_kernel<true>, dim3(std::min<uint32_t>(nt, uint32_t(cus) * 2)), dim3(pbl::kTPB), 0,
+                       st, a);
+    hipLaunchKernelGGL(pbl::row::rwave::row_wave_emit_kernel<kLong>, dim3(nb),
+                       dim3(pbl::row::rwave::kRwWaves * pbl::kWave), 0, st, a);
+  });
+  // the blocks whose key outgrew the emit's stage (listed in the pend area)
+  launch_long_values(a, st, pbl::ws_pend_offset(nb), pbl::row::rowc::kWsBigPend);
   return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
 }
 
@@ -368,6 +400,12 @@ extern "C" {
 int pbl_abi_version(void) { return PBL_ABI_VERSION; }
 
 uint64_t pbl_workspace_bytes(uint32_t n_blocks) { return pbl::ws_alloc_bytes(n_blocks); }
+
+uint64_t pbl_workspace_bytes_for(uint32_t n_blocks, uint32_t max_block_len) {
+  const uint64_t base = pbl::ws_alloc_bytes(n_blocks);
+  if (max_block_len <= pbl::row::kMaxFastLen) return base;
+  return base + uint64_t(pbl::kLongKeyWgs) * ((uint64_t(max_block_len) + 15) & ~uint64_t(15));
+}
 
 int pbl_decode_batch_colblk(const pbl_block_batch* batch, pbl_decode_out* out, void* stream);
 

@@ -27,15 +27,62 @@ enum { kPassCount = 0, kPassAll = 1 };
 #define PBL_SLOW_U 1
 #endif
 
-// U: value granules per lane in flight.
-template <class Src, int U>
+// The spill form's key store past the LDS buffer: a per-workgroup slot in
+// global memory (16-B aligned).  With C the LDS capacity, key byte p lives in
+// LDS for p < C + kSpillSeam and at spill[p - C] for p >= C: the seam bytes are
+// kept in both, so every 16-B window and every trailer comes whole from one of
+// the two (windows that start at or below C from LDS, the rest from the slot).
+constexpr uint32_t kSpillSeam = 16;
+static_assert(kSpillSeam + 16 <= kKeyBufSlack - kKeyBufPad, "the seam and a window past it fit the LDS tail");
+
+// Bytes [lo, hi) of the slot's 16-B granule at ga from w: plain stores (the
+// slot is read back, never streamed past).
+__device__ __forceinline__ void spill_put16(gptr<uint8_t> spill, uint64_t ga, uint64_t lo, uint64_t hi, const uint4& w) {
+  if (ga >= lo && ga + 16 <= hi) {
+    *(gptr<u32x4>)(spill + ga) = u32x4{w.x, w.y, w.z, w.w};
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const uint32_t word = i < 4 ? w.x : i < 8 ? w.y : i < 12 ? w.z : w.w;
+    if (ga + i >= lo && ga + i < hi) spill[ga + i] = uint8_t(word >> (8 * (i & 3)));
+  }
+}
+// Slot reads are served from L2 (agent-scope loads): the CU's L1 may hold the
+// line as it was for an earlier key.  The caller has drained its stores.
+__device__ __forceinline__ uint4 spill_granule(gptr<uint8_t> spill, uint64_t a) {
+  const gptr<uint64_t> q = (gptr<uint64_t>)(spill + a);
+  const uint64_t x = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const uint64_t y = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return make_uint4(uint32_t(x), uint32_t(x >> 32), uint32_t(y), uint32_t(y >> 32));
+}
+// 16 slot bytes at x (any alignment): the aligned pair, funnelled
+__device__ __forceinline__ uint4 spill_get16(gptr<uint8_t> spill, uint64_t x) {
+  const uint64_t a = x & ~uint64_t(15);
+  const uint32_t sh = uint32_t(x - a);
+  const uint4 v = spill_granule(spill, a);
+  return sh ? funnel16(v, spill_granule(spill, a + 16), sh) : v;
+}
+__device__ __forceinline__ uint32_t spill_byte(gptr<uint8_t> spill, uint64_t x) {
+  return __hip_atomic_load(spill + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// U: value granules per lane in flight.  kSpill: keys longer than the LDS
+// buffer continue in the slot `spill` of `spillcap` bytes (the long-key
+// kernels of rowblk_long.hip.h; the block in global memory); every other walk
+// keeps the key in LDS alone.
+template <class Src, int U, bool kSpill = false>
 __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t flags, uint64_t seq, lptr<uint8_t> kbuf,
                                             uint32_t keycap, int pass, const pbl_decode_out& O, uint32_t b,
-                                            const uint64_t bases[kNumComp], SlowState* st) {
+                                            const uint64_t bases[kNumComp], SlowState* st,
+                                            gptr<uint8_t> spill = nullptr, uint64_t spillcap = 0) {
   const int l = lane_id();
   lptr<uint8_t> keybuf = kbuf + kKeyBufPad;
   const lptr<const uint32_t> KW = (lptr<const uint32_t>)kbuf;
   keycap = keycap > kKeyBufSlack ? keycap - kKeyBufSlack : 0;
+  // the longest key the walk holds: the slot keeps kKeyBufSlack bytes for the
+  // windows that end past a key
+  const uint64_t keymax = uint64_t(keycap) + (kSpill && spillcap > kKeyBufSlack ? spillcap - kKeyBufSlack : 0);
   const gptr<uint64_t> o_trailer = to_glb(O.trailer);
   const gptr<uint8_t> o_flags = to_glb(O.kv_flags);
   const gptr<uint32_t> o_entry = to_glb(O.entry_off), o_koff = to_glb(O.key_off), o_voff = to_glb(O.val_off);
@@ -65,24 +112,45 @@ __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t 
     if (len - vp < vlen) { status = PBL_CORRUPT_BOUNDS; break; }
     if (shared > full_len) { status = PBL_CORRUPT_BOUNDS; break; }
     const uint64_t klen = uint64_t(shared) + unshared;
-    if (klen > keycap) { status = PBL_UNSUPPORTED; break; }
+    if (klen > keymax) { status = PBL_UNSUPPORTED; break; }
     if (int64_t(vp + vlen) < restarts) hw_next = S.ld16(int64_t(vp + vlen));
     wave_sync();
     // unshared key bytes -> keybuf[shared, klen): one 16-B window per lane step
-    for (uint32_t i0 = 16u * l; i0 < unshared; i0 += 16u * kWave) {
+    // (the spill form: up to the end of the seam)
+    const uint32_t un_lds =
+        !kSpill ? unshared
+                : uint32_t(min<uint64_t>(klen, uint64_t(keycap) + kSpillSeam) - min<uint64_t>(shared, uint64_t(keycap) + kSpillSeam));
+    for (uint32_t i0 = 16u * l; i0 < un_lds; i0 += 16u * kWave) {
       const uint4 w = S.ld16(int64_t(kp + i0));
-      const uint32_t n = min(16u, unshared - i0);
+      const uint32_t n = min(16u, un_lds - i0);
 #pragma unroll
       for (uint32_t k = 0; k < 16; k++)
         if (k < n) keybuf[shared + i0 + k] = uint8_t(win_byte(w, k));
+    }
+    if constexpr (kSpill) {
+      if (klen > keycap) {
+        // key bytes [max(shared, C), klen) -> the slot, by its 16-B granules;
+        // slot offset x holds block byte d + x
+        const uint64_t lo = max<uint64_t>(shared, keycap) - keycap, hi = klen - keycap;
+        const int64_t d = int64_t(kp) + int64_t(keycap) - int64_t(shared);
+        for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * l; ga < hi; ga += 16ull * kWave)
+          spill_put16(spill, ga, lo, hi, S.ld16(d + int64_t(ga)));
+        // the stores reach L2 before any read of the slot
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
     }
     wave_sync();
     full_len = klen;
     uint64_t trailer, ukl, raw = 0;
     uint32_t fl = 0;
     if (!(flags & PBL_ROW_RAW_KEYS) && klen >= 8) {
+      if (kSpill && klen > uint64_t(keycap) + kSpillSeam) {  // wholly past C
 #pragma unroll
-      for (int i = 0; i < 8; i++) raw |= uint64_t(keybuf[klen - 8 + i]) << (8 * i);
+        for (int i = 0; i < 8; i++) raw |= uint64_t(spill_byte(spill, klen - 8 - keycap + i)) << (8 * i);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) raw |= uint64_t(keybuf[klen - 8 + i]) << (8 * i);
+      }
     }
     split_trailer(raw, klen, flags, &trailer, &ukl, &fl);
     // blockiter.Transforms.HideObsoletePoints: the entry is skipped before its
@@ -123,8 +191,12 @@ __device__ __forceinline__ void slow_walk_t(const Src S, uint64_t len, uint32_t 
       // user key: 16-B destination granules gathered from the key buffer
       {
         const uint64_t lo = bases[1] + kb, hi = lo + ukl;
-        for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * l; ga < hi; ga += 16ull * kWave)
-          store16(O.key_bytes, ga, lo, hi, lds_gather16(KW, uint32_t(int64_t(kKeyBufPad) + int64_t(ga - lo))));
+        for (uint64_t ga = (lo & ~uint64_t(15)) + 16ull * l; ga < hi; ga += 16ull * kWave) {
+          if (kSpill && int64_t(ga - lo) > int64_t(keycap))  // a window past C: from the slot
+            store16(O.key_bytes, ga, lo, hi, spill_get16(spill, (ga - lo) - keycap));
+          else
+            store16(O.key_bytes, ga, lo, hi, lds_gather16(KW, uint32_t(int64_t(kKeyBufPad) + int64_t(ga - lo))));
+        }
       }
     }
     if (pass == kPassAll) {

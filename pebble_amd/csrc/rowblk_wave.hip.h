@@ -49,6 +49,18 @@ namespace rwave {
 
 // the general walk's key limit with the whole stage as its key buffer
 constexpr uint64_t kKeyCapMax = uint64_t(kLdsBlkBytes) - kKeyBufSlack;
+// ... and with the long-key kernels' spill slot behind it, when the caller's
+// workspace holds slots (slow_walk_t's keymax in its spill form): a key is
+// PBL_UNSUPPORTED when it is past the LDS cap and no slot holds the rest
+// The three kernels below are templates on kLong, the form launched for a
+// workspace with slots; the other is the kernel as it was (the limit a
+// constant, no listing in the emit).
+template <bool kLong>
+__device__ __forceinline__ uint64_t key_cap_max(const Args& A) {
+  if (!kLong) return kKeyCapMax;
+  const uint64_t s = ws_spill_slot_bytes(A.out.workspace_bytes, A.in.n_blocks);
+  return kKeyCapMax + (s > kKeyBufSlack ? s - kKeyBufSlack : 0);
+}
 
 // Whether a batch's flags let the size pass count without key bytes.
 __host__ __device__ inline bool sizes_without_keys(uint32_t flags) {
@@ -79,7 +91,7 @@ __device__ __forceinline__ void put_sizes(const pbl_decode_out& O, gptr<uint64_t
 // without the key bytes; at most `limit` entries (then *more is set).
 __device__ __forceinline__ uint32_t seq_count(const GlbBlk& S, uint32_t blen, uint32_t roff, bool raw, uint64_t& off,
                                               uint64_t& full, uint64_t& nkv, uint64_t& kb, uint64_t& vb,
-                                              uint32_t limit, bool* more, gptr<uint16_t> rec) {
+                                              uint32_t limit, bool* more, gptr<uint16_t> rec, uint64_t keymax) {
   uint32_t n = 0;
   *more = false;
   while (off < roff) {
@@ -95,7 +107,7 @@ __device__ __forceinline__ uint32_t seq_count(const GlbBlk& S, uint32_t blen, ui
     if (blen - vp < vlen) return PBL_CORRUPT_BOUNDS;
     if (shared > full) return PBL_CORRUPT_BOUNDS;
     const uint64_t klen = uint64_t(shared) + unshared;
-    if (klen > kKeyCapMax) return PBL_UNSUPPORTED;
+    if (klen > keymax) return PBL_UNSUPPORTED;
     full = klen;
     if (rec && nkv < kEntRec) rec[nkv] = uint16_t(off);  // (for the emit)
     nkv++;
@@ -107,6 +119,7 @@ __device__ __forceinline__ uint32_t seq_count(const GlbBlk& S, uint32_t blen, ui
   return (kb >> 32 || vb >> 32) ? PBL_UNSUPPORTED : PBL_OK;
 }
 
+template <bool kLong>
 __global__ void __launch_bounds__(kWave) row_wave_size_kernel(Args A) {
   const uint32_t nb = A.in.n_blocks, flags = A.in.flags;
   const pbl_decode_out& O = A.out;
@@ -116,6 +129,7 @@ __global__ void __launch_bounds__(kWave) row_wave_size_kernel(Args A) {
   const gptr<uint16_t> rec = to_glb(reinterpret_cast<uint16_t*>(ws + ws_ent_offset(nb)));
   uint32_t* hdr = reinterpret_cast<uint32_t*>(ws);
   const gptr<uint32_t> dense_ids = to_glb(reinterpret_cast<uint32_t*>(ws + ws_redo_offset(nb)));
+  const uint64_t keymax = key_cap_max<kLong>(A);
   for (uint64_t b0 = uint64_t(blockIdx.x) * kWave; b0 < nb; b0 += uint64_t(gridDim.x) * kWave) {
     const uint64_t b = b0 + lane_id();
     bool dense = false;
@@ -130,7 +144,7 @@ __global__ void __launch_bounds__(kWave) row_wave_size_kernel(Args A) {
         const gptr<uint16_t> r = blen <= kMaxFastLen ? rec + b * kEntRec : gptr<uint16_t>(nullptr);
         uint64_t off = 0, full = 0;
         bool more = false;
-        status = seq_count(S, blen, roff, raw, off, full, nkv, kb, vb, kDenseProbe, &more, r);
+        status = seq_count(S, blen, roff, raw, off, full, nkv, kb, vb, kDenseProbe, &more, r, keymax);
         if (status == PBL_OK && more) {
           // at this pace more than 2 kEntRec entries, in at least eight
           // restart runs to walk side by side (config 5 RI 16 with the
@@ -141,7 +155,7 @@ __global__ void __launch_bounds__(kWave) row_wave_size_kernel(Args A) {
           if (dense) {
             if (r) r[0] = 0xffffu;
           } else {
-            status = seq_count(S, blen, roff, raw, off, full, nkv, kb, vb, ~0u, &more, r);
+            status = seq_count(S, blen, roff, raw, off, full, nkv, kb, vb, ~0u, &more, r, keymax);
           }
         }
       }
@@ -163,6 +177,7 @@ __global__ void __launch_bounds__(kWave) row_wave_size_kernel(Args A) {
 // with shared 0, each run ending at the next run's start).  Where the runs tile
 // the entries exactly and every entry is clean, the per-run sums ARE the
 // sequential walk's; any other block is counted by seq_count (lane 0).
+template <bool kLong>
 __global__ void __launch_bounds__(kWave) row_wave_dense_kernel(Args A) {
   const uint32_t nb = A.in.n_blocks, flags = A.in.flags;
   const pbl_decode_out& O = A.out;
@@ -173,6 +188,7 @@ __global__ void __launch_bounds__(kWave) row_wave_dense_kernel(Args A) {
   const uint32_t* hdr = reinterpret_cast<const uint32_t*>(ws);
   const uint32_t n = __hip_atomic_load(to_glb(hdr) + rowc::kWsBigRedo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const gptr<const uint32_t> dense_ids = to_glb(reinterpret_cast<const uint32_t*>(ws + ws_redo_offset(nb)));
+  const uint64_t keymax = key_cap_max<kLong>(A);
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
     const uint32_t b = dense_ids[i];
     const uint32_t blen = to_glb(A.in.block_len)[b];
@@ -194,7 +210,7 @@ __global__ void __launch_bounds__(kWave) row_wave_dense_kernel(Args A) {
         const uint32_t h = entry_header(hw, hn, &shared, &unshared, &vlen);
         const uint64_t np = off + h + unshared + vlen;
         const uint64_t klen = uint64_t(shared) + unshared;
-        if (!h || np > e0 || (first ? shared != 0 : shared > prev) || klen > kKeyCapMax) { ok = false; break; }
+        if (!h || np > e0 || (first ? shared != 0 : shared > prev) || klen > keymax) { ok = false; break; }
         nkv++;
         kb += raw ? klen : (klen >= 8 ? klen - 8 : 0);
         vb += vlen;
@@ -212,7 +228,7 @@ __global__ void __launch_bounds__(kWave) row_wave_dense_kernel(Args A) {
       uint64_t off = 0, full = 0;
       bool more;
       nkv = kb = vb = 0;
-      status = seq_count(S, blen, roff, raw, off, full, nkv, kb, vb, ~0u, &more, gptr<uint16_t>(nullptr));
+      status = seq_count(S, blen, roff, raw, off, full, nkv, kb, vb, ~0u, &more, gptr<uint16_t>(nullptr), keymax);
     }
     if (l == 0) put_sizes(O, rcnt, b, status, nkv, kb, vb, nres);
   }
@@ -227,7 +243,9 @@ __global__ void __launch_bounds__(kWave) row_wave_dense_kernel(Args A) {
 // than a slot holds, an empty or failing block, sizes that disagree with the
 // size pass) takes the wave-serial general walk on the stage with the slot as
 // its key buffer; a key past the slot, or a block past the stage, walks global
-// memory with the stage as the key buffer (as block_slow does).
+// memory with the stage as the key buffer (as block_slow does); a key past
+// that lists the block for long_key_values_kernel (rowblk_long.hip.h), which
+// has a spill slot for it.
 #ifndef PBL_RW_FAST
 #define PBL_RW_FAST 1  // 0: every block on the general walk (A/B)
 #endif
@@ -444,6 +462,7 @@ __device__ __forceinline__ RDesc load_desc(const Args& A, uint32_t b) {
 }
 
 // One block of the emit (both waves).
+template <bool kLong>
 __device__ __forceinline__ void emit_block(ELds& L, uint32_t* s_fast, const Args& A, uint32_t b, const RDesc& d) {
   const int l = lane_id();
   const bool w0 = kRwWaves == 1 || wave_id() == 0;
@@ -541,7 +560,13 @@ __device__ __forceinline__ void emit_block(ELds& L, uint32_t* s_fast, const Args
                                       to_lds_ptr(reinterpret_cast<uint8_t*>(L.st.x)), uint32_t(sizeof(L.st)),
                                       kPassAll, O, b, excl, &ss);
     PSTAMP(A, b, 4, l == 0);
-    if (ss.status != PBL_OK && l == 0) {
+    if (kLong && ss.status == PBL_UNSUPPORTED && key_cap_max<kLong>(A) > kKeyCapMax && l == 0) {
+      // a key past the stage (the size pass found a spill slot for it): the
+      // long-key values kernel, after this launch, writes the block
+      uint32_t* hdr = reinterpret_cast<uint32_t*>(O.workspace);
+      uint32_t* pend = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(O.workspace) + ws_pend_offset(nb));
+      to_glb(pend)[g_atomic_add(hdr + rowc::kWsBigPend, 1u)] = b;
+    } else if (ss.status != PBL_OK && l == 0) {
       // the walk the size pass restated cannot disagree with it; if it ever
       // did, the block reports the walk's status
       to_glb(O.blk_status)[b] = ss.status;
@@ -555,11 +580,12 @@ __device__ __forceinline__ void emit_block(ELds& L, uint32_t* s_fast, const Args
 // blocks with the next block's descriptor prefetched measured slower: 1408 /
 // 1310 GiB/s with static / ticketed assignment against 1475 on config 5 RI
 // 16; the dispatcher's own refill hides a new workgroup's first round trip.)
+template <bool kLong>
 __global__ void __launch_bounds__(kRwWaves * kWave) row_wave_emit_kernel(Args A) {
   __shared__ ELds L;
   __shared__ uint32_t s_fast;  // the block took the lane-parallel form (roff + 1), else 0
   const uint32_t b = blockIdx.x;
-  emit_block(L, &s_fast, A, b, load_desc(A, b));
+  emit_block<kLong>(L, &s_fast, A, b, load_desc(A, b));
 }
 
 }  // namespace rwave

@@ -86,4 +86,5 @@ def decompress(pb: PhysBatch, fmt: int = N.PBL_FMT_ROW, flags: int = 0, stream=N
     if rc != N.PBL_OK:
         raise DecodeError(f"pbl_decompress_blocks: {N.STATUS_NAMES.get(rc, rc)}")
     status = st[:n].cpu().numpy().view(np.uint32).copy()
-    return BlockBatch(out, off_t, lens[:n].clone(), fmt, flags | varlen_hint(hl.astype(np.uint32))), status
+    return BlockBatch(out, off_t, lens[:n].clone(), fmt, flags | varlen_hint(hl.astype(np.uint32)),
+                      max_block_len=int(hl.max()) if n else 0), status

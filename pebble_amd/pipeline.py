@@ -63,7 +63,11 @@ class HostOutputs:
 
 
 class HostPipeline:
-    """Reusable device state for streaming host batches (one device)."""
+    """Reusable device state for streaming host batches (one device).  The
+    outputs are allocated before any block is seen, with the workspace of
+    pbl_workspace_bytes: a row block with a key longer than 32 KiB reports
+    PBL_UNSUPPORTED here (key spill slots for the longest possible block, the
+    chunk itself, would cost 32 x chunk_bytes per slot of the pipeline)."""
 
     def __init__(self, device, chunk_blocks: int, chunk_bytes: int, per_chunk: Capacity, slots: int = 3):
         self.dev = torch.device(device)
