@@ -282,6 +282,9 @@ static int64_t huf_read(HufTab* H, const uint8_t* src, uint64_t n) {
   /* table: weight 1 first, symbols in order within a weight (HUF_readDTableX1) */
   uint32_t start[13] = {0}, cnt[13] = {0};
   for (int i = 0; i < nw; i++) cnt[w[i]]++;
+  /* HUF_readStats: a tree's longest codes come in pairs ("at least 2 elts of
+   * rank 1, must be even"); a description without them is corrupt */
+  if (cnt[1] < 2 || (cnt[1] & 1)) return -1;
   uint32_t acc = 0;
   for (int k = 1; k <= log; k++) {
     start[k] = acc;

@@ -348,6 +348,8 @@ __device__ inline int32_t huf_read(LT& L, const S& s, uint32_t base, uint32_t n,
       // HUF_readDTableX1: weight 1 first, symbols in order within a weight
       uint32_t cnt[13] = {0}, start[13] = {0};
       for (uint32_t i = 0; i < nw; i++) cnt[w[i]]++;
+      // HUF_readStats: the longest codes come in pairs (at least two symbols of weight 1)
+      if (cnt[1] < 2 || (cnt[1] & 1)) ok = false;
       uint32_t acc = 0;
       for (uint32_t k = 1; k <= log; k++) {
         start[k] = acc;

@@ -5,9 +5,14 @@ zstdDecompressor calls: internal/compression/zstd_cgo.go:86-108), pinned by
   * the reference's zstd table, sstable/testdata/h-zstd-compression-sst/000004.sst:
     every data block decodes to blocks whose KVs are exactly h.txt's;
   * frames written by facebook/zstd itself (the codec pyarrow bundles) at
-    levels -5..19 over random, repetitive and text-like inputs, exercising
-    raw / RLE / compressed blocks, raw / RLE / Huffman / treeless literals with
-    1 and 4 streams, and predefined / RLE / FSE / repeat sequence tables;
+    levels -5..19 over random, repetitive and text-like inputs.  By census
+    (tests/zstdutil.py) they hold raw / RLE / compressed blocks, multi-block
+    frames, raw / Huffman (FSE-coded weights, 1 and 4 streams, every size
+    format) / treeless literals and predefined / FSE / repeat sequence tables,
+    every second frame with a content checksum; the library never emits RLE
+    literals, direct Huffman weights, RLE tables, the 3-byte sequence count
+    or the other header forms on request: tests/test_zstd_forms.py assembles
+    those and holds the oracle to facebook/zstd on them;
   * XXH64 against the xxhash package (the content checksum);
 and corrupt inputs (truncations, flipped bytes) never decode to a wrong length."""
 import json
@@ -17,6 +22,8 @@ import random
 import pytest
 
 import oracle
+import zstdutil
+from zstdutil import corpus
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 with open(os.path.join(GOLDEN, "physical.json")) as f:
@@ -25,19 +32,9 @@ BLOB = open(os.path.join(GOLDEN, "physical_blocks.bin"), "rb").read()
 
 
 def zstd(data: bytes, level: int, checksum: bool = False) -> bytes:
-    import pyarrow as pa
-    return pa.Codec("zstd", compression_level=level).compress(data, asbytes=True)
-
-
-def corpus(rng, kind, n):
-    words = [bytes(rng.choice(b"abcdefghij") for _ in range(rng.randint(2, 9))) for _ in range(300)]
-    if kind == 0:
-        return rng.randbytes(n)
-    if kind == 1:
-        return b" ".join(rng.choice(words) for _ in range(n // 5 + 1))[:n]
-    if kind == 2:
-        return bytes([rng.choice(b"ab")]) * n
-    return b"".join(rng.choice(words) + rng.randbytes(rng.randint(0, 3)) for _ in range(n // 6 + 1))[:n]
+    """A facebook/zstd frame; checksum=True sets the frame header's checksum
+    flag and appends XXH64(data)'s low 32 bits (zstdutil.add_checksum)."""
+    return zstdutil.compress(data, level, checksum)
 
 
 def test_h_zstd_blocks_decode_to_hamlet(golden):
@@ -62,10 +59,13 @@ def test_frames_from_the_zstd_library(level):
     for trial in range(60):
         n = rng.choice([0, 1, 5, 100, 1000, 5000, 32768, 70000, 140000])
         data = corpus(rng, trial % 4, n)
-        c = zstd(data, level)
+        c = zstd(data, level, checksum=trial % 2 == 1)
         assert oracle.zstd_decompress(c, len(data) + 8) == data, (trial, n)
         if n:
             assert oracle.zstd_decompress(c, len(data) - 1) == -3  # output too small
+        if trial % 2 == 1:
+            assert zstdutil.libzstd(c, len(data)) == data
+            assert oracle.zstd_decompress(c[:-1] + bytes([c[-1] ^ 0x10]), len(data) + 8) == -1, (trial, n)
 
 
 def test_xxh64_against_xxhash():

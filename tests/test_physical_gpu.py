@@ -6,7 +6,17 @@ agree with the oracle on random inputs (single-wave LDS path and the >32 KiB
 global path), corrupt snappy is rejected; zstd blocks (h-zstd-compression-sst)
 decompress on the device to exactly h.txt's KVs, and random zstd frames made
 by facebook/zstd (pyarrow's codec) at levels -5..19 decode to the oracle's
-bytes on both the LDS and the global path, corrupt ones as the oracle says."""
+bytes on both the LDS and the global path, corrupt ones as the oracle says.
+
+What the zstd corpora here hold (tests/zstdutil.py's census): compressible()
+draws its words from randbytes, so the library stores every literals section
+raw and codes the sequences with predefined and FSE tables only; no frame has
+a checksum or a window descriptor, and the one multi-block frame is raw / RLE
+blocks.  The h_zstd blocks are 4-stream Huffman literals of at most 1023
+bytes with FSE-coded weights.  Every other form (larger Huffman literals,
+direct weights, treeless and RLE literals, RLE and repeat tables, the 3-byte
+sequence count, the checksum, the header variants, the batch path's
+sequence area running out) is in tests/test_zstd_forms_gpu.py."""
 import os
 import random
 

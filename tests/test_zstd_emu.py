@@ -2,7 +2,12 @@
 host by scripts/zstd_emu.cpp -- 64 threads in lockstep at every wave primitive
 -- against the oracle: h-zstd-compression-sst's blocks and facebook/zstd
 frames, on both the LDS and the global-memory paths.  CPU-only: it checks the
-same source the GPU build compiles, before the GPU runs it."""
+same source the GPU build compiles, before the GPU runs it.
+
+The frames here have raw literals (their words come from randbytes) and
+predefined or FSE sequence tables; the h_zstd blocks add 4-stream Huffman
+literals of at most 1023 bytes.  tests/test_zstd_forms.py runs every other
+form through the same emulator."""
 import os
 import random
 import shutil
