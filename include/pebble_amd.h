@@ -752,6 +752,101 @@ int pbl_data_iter_is_data_invalidated(const pbl_data_iter* it);
 int pbl_key_compare(uint32_t comparer, const uint8_t* a, uint64_t a_len, const uint8_t* b, uint64_t b_len);
 uint64_t pbl_key_split(uint32_t comparer, const uint8_t* key, uint64_t key_len);
 
+/* ---- batched SeekGE / SeekLT over a decoded batch, on the device ----
+ * Many keys positioned in one stream-ordered launch over the arrays a decode
+ * left in device memory: no copy to the host, no per-key call.  The semantics
+ * are the host iterator's above (same comparers, same HideObsoletePoints skip).
+ *
+ * `decoded` is a HOST struct of DEVICE arrays exactly as pbl_decode_batch left
+ * it (or pbl_transform_batch, or pbl_resolve_values: the convention of
+ * pbl_transform_batch's `in`).  blk_status, blk_kv_base, blk_key_base, key_off
+ * and key_bytes are needed; kv_flags only with hide_obsolete_points.  key_bytes
+ * and the queries' key_bytes must be readable 16 B past their end (keys are
+ * compared 16 B at a time; pebble_amd's allocations pad).
+ *
+ * Per-block mode (q->block != NULL): blockiter.Data.SeekGE / SeekLT
+ * (sstable/blockiter/block_iter.go:19-108; rowblk_iter.go:606-781, :782-1054)
+ * in block q->block[i]: the result equals pbl_data_iter_init(block, comparer,
+ * hide) followed by pbl_data_iter_seek_ge / _seek_lt.  out.kv = the landing
+ * KV's index blk_kv_base[b] + j, or PBL_SEEK_NONE where the iterator returns
+ * NULL.  A block id >= n_blocks, or a block whose status is not PBL_OK, gives
+ * PBL_SEEK_NONE with PBL_SEEK_BAD_BLOCK (the entry points are asynchronous: it
+ * cannot be a return code).  Needs no workspace (NULL, 0).
+ *
+ * Table mode (q->block == NULL): singleLevelIterator.SeekGE / SeekLT
+ * (sstable/reader_iter_single_lvl.go:757-898: index.SeekGE, data.SeekGE, then
+ * on into the next block when this one is exhausted).  SeekGE: the first
+ * visible KV, in batch order, whose user key is >= the query; SeekLT: the last
+ * visible KV whose user key is < the query; PBL_SEEK_NONE past either end.
+ * Blocks whose status is not PBL_OK are passed over: a corrupt block publishes
+ * zero KVs, key bytes and value bytes (its look-back aggregate is zero in every
+ * decode kernel, e.g. rowblk_pool.hip.h block_describe), so it owns no KV index;
+ * a block that reports PBL_OVERFLOW keeps its index range but nothing of it was
+ * written, and it is passed over by its status like the others.  With
+ * hide_obsolete_points the skip over hidden KVs crosses any number of block
+ * boundaries.  Precondition: user keys are non-decreasing under `comparer` over
+ * the whole batch, as a table's data blocks are.  For an unordered batch the
+ * result is unspecified, but every read stays in bounds and the kernel
+ * terminates.
+ *
+ * pbl_seek_prepare builds what table mode needs in `workspace` (DEVICE,
+ * 16-byte aligned, pbl_seek_workspace_bytes(n_blocks)): the fence table, one
+ * 32-byte record per PBL_OK block that holds a KV, in batch order -- the first
+ * 16 bytes of the block's last user key's Split-prefix, so that most steps of
+ * the search over blocks are decided without touching key_bytes.  Two
+ * launches, no host read.  The workspace is read-only afterwards: any number of
+ * pbl_seek_batch calls, on any stream ordered after the prepare, reuse it.  It
+ * is bound to one comparer and one batch, and using it with q->comparer equal to
+ * prepare's is the caller's precondition: the host keeps no state and reads no
+ * device memory, so this cannot be a return code.  The kernel checks it
+ * instead: the comparer and n_blocks are recorded in the workspace header, and
+ * a table-mode launch that finds another comparer, another n_blocks or no
+ * header answers every query PBL_SEEK_NONE with PBL_SEEK_BAD_BLOCK.
+ *
+ * PBL_INVALID_ARG, before any device call: comparer > PBL_CMP_CRDB, op >
+ * PBL_SEEK_LT, NULL decoded / q / out, NULL out->kv, NULL q->key_off, a needed
+ * array of `decoded` NULL, a workspace that is not 16-byte aligned or shorter
+ * than pbl_seek_workspace_bytes(n_blocks), table mode without a workspace.
+ * n == 0 returns PBL_OK without a launch.
+ */
+#define PBL_SEEK_GE 0u
+#define PBL_SEEK_LT 1u
+#define PBL_SEEK_NONE UINT64_MAX      /* out.kv: no KV (exhausted) */
+#define PBL_SEEK_EXACT       0x1u     /* landing KV's user key compares equal to the query (GE only) */
+#define PBL_SEEK_SAME_PREFIX 0x2u     /* landing KV's Split-prefix equals the query's (what SeekPrefixGE
+                                         tests, rowblk_iter.go:550-564) */
+#define PBL_SEEK_BAD_BLOCK   0x4u     /* per-block mode: the named block is past n_blocks or its status !=
+                                         PBL_OK; table mode: the workspace is not this batch's and comparer's */
+
+typedef struct pbl_seek_queries {
+  const uint8_t*  key_bytes;  /* DEVICE; readable 16 B past the last key */
+  const uint64_t* key_off;    /* DEVICE [n + 1] */
+  const uint32_t* block;      /* DEVICE [n], or NULL (see modes) */
+  uint32_t n, comparer /* PBL_CMP_* */, op /* PBL_SEEK_* */, hide_obsolete_points;
+} pbl_seek_queries;
+
+typedef struct pbl_seek_out {
+  uint64_t* kv;     /* DEVICE [n] global KV index (blk_kv_base[b] + j) or PBL_SEEK_NONE */
+  uint32_t* block;  /* DEVICE [n], optional: block of the landing KV (0 with PBL_SEEK_NONE) */
+  uint8_t*  flags;  /* DEVICE [n], optional: PBL_SEEK_* flag bits */
+} pbl_seek_out;
+
+uint64_t pbl_seek_workspace_bytes(uint32_t n_blocks);
+int pbl_seek_prepare(const pbl_decode_out* decoded, uint32_t n_blocks, uint32_t comparer,
+                     void* workspace, uint64_t workspace_bytes, void* stream);
+int pbl_seek_batch(const pbl_decode_out* decoded, uint32_t n_blocks, const pbl_seek_queries* q,
+                   pbl_seek_out* out, const void* workspace, uint64_t workspace_bytes, void* stream);
+/* The same search (one function, seek.hip seek_one) over arrays in HOST memory
+ * (DecodedBatch.to_host(), the oracle's arrays): every pointer of `host`, `q`
+ * and `out` is a host pointer; no device call; nothing is read past a key's
+ * end.  Table mode builds its fence per call.  Single-threaded. */
+int pbl_seek_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl_seek_queries* q,
+                        pbl_seek_out* out);
+/* Layout of the two structs above, as pbl_struct_layout reports the others
+ * (whose list is unchanged): sizeof(pbl_seek_queries), its 7 field offsets,
+ * sizeof(pbl_seek_out), its 3 field offsets. */
+size_t pbl_seek_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

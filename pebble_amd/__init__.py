@@ -7,6 +7,7 @@ C-ABI declared in include/pebble_amd.h.  This package is the host layer:
   pebble_amd.batch   BlockBatch / decode() / DecodedBatch (device buffers, streams)
   pebble_amd.rowblk  Writer, NewIter/Iter mirroring sstable/rowblk
   pebble_amd.shard   multi-GPU sharding + RCCL offset concat
+  pebble_amd.seek    batched SeekGE / SeekLT over a DecodedBatch, on the device
 """
 from . import _native  # noqa: F401
 

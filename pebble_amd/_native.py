@@ -180,6 +180,21 @@ PBL_CMP_DEFAULT, PBL_CMP_TESTKEYS, PBL_CMP_CRDB = 0, 1, 2
 _kvp = ctypes.POINTER(KvC)
 _u8p = ctypes.c_char_p
 
+# batched seeks (pbl_seek_batch)
+PBL_SEEK_GE, PBL_SEEK_LT = 0, 1
+PBL_SEEK_NONE = (1 << 64) - 1
+PBL_SEEK_EXACT, PBL_SEEK_SAME_PREFIX, PBL_SEEK_BAD_BLOCK = 0x1, 0x2, 0x4
+
+
+class SeekQueriesC(ctypes.Structure):  # pbl_seek_queries
+    _fields_ = [("key_bytes", _vp), ("key_off", _vp), ("block", _vp), ("n", ctypes.c_uint32),
+                ("comparer", ctypes.c_uint32), ("op", ctypes.c_uint32), ("hide_obsolete_points", ctypes.c_uint32)]
+
+
+class SeekOutC(ctypes.Structure):  # pbl_seek_out
+    _fields_ = [("kv", _vp), ("block", _vp), ("flags", _vp)]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -207,6 +222,14 @@ SIGNATURES = {
     "pbl_data_iter_is_data_invalidated": (ctypes.c_int, [_vp]),
     "pbl_key_compare": (ctypes.c_int, [ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, ctypes.c_uint64]),
     "pbl_key_split": (ctypes.c_uint64, [ctypes.c_uint32, _u8p, ctypes.c_uint64]),
+    "pbl_seek_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "pbl_seek_prepare": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                        ctypes.c_uint64, _vp]),
+    "pbl_seek_batch": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32, ctypes.POINTER(SeekQueriesC),
+                                      ctypes.POINTER(SeekOutC), _vp, ctypes.c_uint64, _vp]),
+    "pbl_seek_batch_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
+                                           ctypes.POINTER(SeekQueriesC), ctypes.POINTER(SeekOutC)]),
+    "pbl_seek_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

@@ -13,10 +13,8 @@
 // (blockiter.Transforms) skips KVs whose trailer carried the obsolete bit
 // (PBL_KV_OBSOLETE), as :1168-1179.  *_with_meta: colblk.DataBlockIter's
 // FirstWithMeta / NextWithMeta / SeekGEWithMeta (sstable/colblk/data_block.go:
-// 1574-1600, decodeMeta :1633-1641) over the decoded KVMeta arrays.  Comparers: base.DefaultComparer
-// (internal/base/comparer.go: bytes.Compare, Split = len), testkeys.Comparer
-// (internal/testkeys/testkeys.go:136-171) and cockroachkvs.Comparer
-// (cockroachkvs/cockroachkvs.go:298-339, :479-...).
+// 1574-1600, decodeMeta :1633-1641) over the decoded KVMeta arrays.  The three
+// comparers are stated in key_cmp.hip.h.
 #include <stdint.h>
 #include <string.h>
 
@@ -24,6 +22,7 @@
 #include <new>
 
 #include "../../include/pebble_amd.h"
+#include "key_cmp.hip.h"
 
 struct pbl_data_iter {
   const uint64_t* trailer = nullptr;
@@ -48,94 +47,13 @@ struct pbl_data_iter {
 
 namespace {
 
-int bytes_cmp(const uint8_t* a, uint64_t al, const uint8_t* b, uint64_t bl) {
-  const int c = memcmp(a, b, std::min(al, bl));
-  if (c) return c < 0 ? -1 : 1;
-  return al < bl ? -1 : al > bl ? 1 : 0;
-}
-
-// ---- testkeys.Comparer -------------------------------------------------------
-uint64_t tk_split(const uint8_t* a, uint64_t n) {
-  for (uint64_t i = n; i > 0; i--)
-    if (a[i - 1] == '@') return i - 1;
-  return n;
-}
-// "@N" -> N (parseUintBytes base 10); malformed suffixes (Go panics) sort by bytes
-bool tk_ts(const uint8_t* s, uint64_t n, uint64_t* v) {
-  static const char kIgn[] = "_synthetic";
-  const uint64_t il = sizeof(kIgn) - 1;
-  if (n >= il && memcmp(s + n - il, kIgn, il) == 0) n -= il;
-  if (n < 2 || s[0] != '@') return false;
-  uint64_t x = 0;
-  for (uint64_t k = 1; k < n; k++) {
-    if (s[k] < '0' || s[k] > '9') return false;
-    x = x * 10 + (s[k] - '0');
-  }
-  *v = x;
-  return true;
-}
-uint64_t tk_trim(const uint8_t* s, uint64_t n) {
-  static const char kIgn[] = "_synthetic";
-  const uint64_t il = sizeof(kIgn) - 1;
-  return (n >= il && memcmp(s + n - il, kIgn, il) == 0) ? n - il : n;
-}
-int tk_cmp(const uint8_t* a, uint64_t al, const uint8_t* b, uint64_t bl) {
-  const uint64_t ai = tk_split(a, al), bi = tk_split(b, bl);
-  const int c = bytes_cmp(a, ai, b, bi);
-  if (c) return c;
-  const uint64_t as = tk_trim(a + ai, al - ai), bs = tk_trim(b + bi, bl - bi);
-  if (as == 0 || bs == 0) return as < bs ? -1 : as > bs ? 1 : 0;  // the empty suffix sorts first
-  uint64_t x, y;
-  if (!tk_ts(a + ai, al - ai, &x) || !tk_ts(b + bi, bl - bi, &y)) return bytes_cmp(a + ai, as, b + bi, bs);
-  return y < x ? -1 : y > x ? 1 : 0;  // cmp.Compare(bi, ai): newer first
-}
-
-// ---- cockroachkvs.Comparer ---------------------------------------------------
-uint64_t crdb_split(const uint8_t* a, uint64_t n) {  // cockroachkvs.go:298-311
-  if (n == 0) return 0;
-  const uint64_t s = uint64_t(a[n - 1]);
-  return s <= n ? n - s : 0;
-}
-// normalizeEngineSuffixForCompare (cockroachkvs.go): the suffix without its
-// length byte, with a zero logical component and a synthetic bit dropped so that
-// equal timestamps compare equal
-uint64_t crdb_norm(const uint8_t* s, uint64_t n) {
-  if (n == 0) return 0;
-  uint64_t v = n - 1;  // the version, without the length byte
-  // engineKeyVersionWallLogicalAndSyntheticTimeLen = 13, WallAndLogical = 12,
-  // WallTime = 8: drop the synthetic byte, then a zero logical
-  if (v == 13) v = 12;
-  if (v == 12) {
-    const uint8_t* lg = s + 8;
-    if (lg[0] == 0 && lg[1] == 0 && lg[2] == 0 && lg[3] == 0) v = 8;
-  }
-  return v;
-}
-int crdb_cmp(const uint8_t* a, uint64_t al, const uint8_t* b, uint64_t bl) {  // cockroachkvs.go:313-339
-  if (al == 0 || bl == 0) return al < bl ? -1 : al > bl ? 1 : 0;
-  const uint64_t asl = a[al - 1], bsl = b[bl - 1];
-  const uint64_t ass = asl <= al ? al - asl : 0, bss = bsl <= bl ? bl - bsl : 0;
-  const int c = bytes_cmp(a, ass, b, bss);
-  if (c) return c;
-  if (asl == 0 || bsl == 0) return asl < bsl ? -1 : asl > bsl ? 1 : 0;
-  const uint64_t an = crdb_norm(a + ass, al - ass), bn = crdb_norm(b + bss, bl - bss);
-  return bytes_cmp(b + bss, bn, a + ass, an);  // descending versions
-}
-
+// The comparers: key_cmp.hip.h states them once, for this adapter and for the
+// batched seeks (seek.hip) alike.
+using R = pbl::cmp::HostReader;
 int key_cmp(uint32_t cmp, const uint8_t* a, uint64_t al, const uint8_t* b, uint64_t bl) {
-  switch (cmp) {
-    case PBL_CMP_TESTKEYS: return tk_cmp(a, al, b, bl);
-    case PBL_CMP_CRDB: return crdb_cmp(a, al, b, bl);
-    default: return bytes_cmp(a, al, b, bl);
-  }
+  return pbl::cmp::key_cmp<R>(cmp, a, al, b, bl);
 }
-uint64_t key_split(uint32_t cmp, const uint8_t* a, uint64_t n) {
-  switch (cmp) {
-    case PBL_CMP_TESTKEYS: return tk_split(a, n);
-    case PBL_CMP_CRDB: return crdb_split(a, n);
-    default: return n;
-  }
-}
+uint64_t key_split(uint32_t cmp, const uint8_t* a, uint64_t n) { return pbl::cmp::key_split<R>(cmp, a, n); }
 
 inline const uint8_t* ukey(const pbl_data_iter* it, int64_t j, uint64_t* len) {
   *len = uint64_t(it->key_off[j + 1]) - it->key_off[j];

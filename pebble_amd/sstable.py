@@ -51,6 +51,9 @@ INDEX_TYPE_PROP = b"rocksdb.block.based.table.index.type"
 KEY_SCHEMA_PROP = b"pebble.colblk.schema"
 PROPERTIES_NAME = b"rocksdb.properties"
 VALUE_INDEX_NAME = b"pebble.value_index"
+COMPARER_PROP = b"rocksdb.comparator"
+COMPARERS = {b"leveldb.BytewiseComparator": N.PBL_CMP_DEFAULT, b"pebble.internal.testkeys": N.PBL_CMP_TESTKEYS,
+             b"cockroach_comparator": N.PBL_CMP_CRDB}
 
 
 @dataclass
@@ -239,6 +242,7 @@ class Table:
         self._meta = None
         self._meta_raw = None
         self._props = None
+        self._seek = None
 
     # -- the physical step for any set of handles already on the device ----------
     def _blocks(self, off: torch.Tensor, length: torch.Tensor, fmt: int, flags: int = 0) -> BlockBatch:
@@ -404,3 +408,43 @@ class Table:
             if vb is not None:
                 d = resolve_values(d, vb)
         return d
+
+    # -- positioning: batched seeks over the decoded table (pebble_amd.seek) --------
+    def comparer(self) -> int:
+        """PBL_CMP_* of the table's "rocksdb.comparator" property (the name
+        sstable.Reader checks against Options.Comparer, reader.go:1223-1235);
+        any other name is an error."""
+        name = self.properties().get(COMPARER_PROP, b"")
+        if name not in COMPARERS:
+            raise DecodeError(f"unknown comparer {name!r}")
+        return COMPARERS[name]
+
+    def _seekable(self):
+        """The table decoded once, with its fence table."""
+        if self._seek is None:
+            from .seek import prepare
+            comparer = self.comparer()
+            d = self.decode(resolve=False)
+            if d.read_totals().status_mask:
+                raise DecodeError("corrupt data block")
+            self._seek = (d, prepare(d, comparer))
+        return self._seek
+
+    def _seek_op(self, keys, op: str):
+        from .seek import seek
+        d, idx = self._seekable()
+        return seek(d, keys, op=op, comparer=idx.comparer, index=idx)
+
+    def seek_ge(self, keys):
+        """singleLevelIterator.SeekGE of every key: a SeekResult over the KV
+        indexes of `decode()`."""
+        return self._seek_op(keys, "ge")
+
+    def seek_lt(self, keys):
+        return self._seek_op(keys, "lt")
+
+    def get(self, keys) -> torch.Tensor:
+        """Per key, the index of the first KV whose user key equals it
+        (PBL_SEEK_EXACT), else -1: int64 [n]."""
+        r = self.seek_ge(keys)
+        return torch.where((r.flags & N.PBL_SEEK_EXACT) != 0, r.kv, torch.full_like(r.kv, -1))
