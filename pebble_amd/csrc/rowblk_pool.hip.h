@@ -18,8 +18,14 @@
 //   meta      per-entry metadata words (key source, shared and key length,
 //             prefix parent, header length, flags) and per-KV value offsets
 //             written from the registers into the slot; the stage is released
+//             (before this pass when it reads the registers only:
+//             PBL_POOL_EARLYREL)
 //   resolve   the exclusive prefix by decoupled look-back, issued together
 //             with the first step's and the restart words' loads
+//   prefetch  (PBL_POOL_PREFETCH, off by default: measured slower, DESIGN.md
+//             3.1) under the emit's last steps: a free stage if there is
+//             one, the next ticket and that block's DMA, so the next acquire
+//             / stage find their work done
 //   steps     64 KVs per step, keys and values together (a line of the block
 //             is fetched once for both), each step's loads issued before the
 //             previous step's stores:
@@ -63,6 +69,27 @@ namespace pool {
 #ifndef PBL_POOL_PRIO
 #define PBL_POOL_PRIO 2  // the stage holder's issue priority (the emits run at 0)
 #endif
+// PBL_POOL_EARLYREL: the stage goes back to the pool right after the walk when
+// the metadata pass does not read it (no value prefixes, every run within the
+// parked registers).  0: after the metadata pass, always; 1: early, the
+// metadata pass at the emit's priority; 2: early, PBL_POOL_PRIO kept until the
+// metadata pass is done.
+#ifndef PBL_POOL_EARLYREL
+#define PBL_POOL_EARLYREL 2
+#endif
+// PBL_POOL_PREFETCH: the wave's next block is staged under its emit, the DMA
+// issued before the loads of the emit step this many steps before the last
+// one (a block with fewer steps: before its first stores).  0: off.
+#ifndef PBL_POOL_PREFETCH
+#define PBL_POOL_PREFETCH 0  // compiled out: the measurements are in DESIGN.md 3.1
+#endif
+// PBL_POOL_PREFETCH_LATE 1: one step later than that (PBL_POOL_PREFETCH 1:
+// before the last step's stores, after every load of the emit).
+#ifndef PBL_POOL_PREFETCH_LATE
+#define PBL_POOL_PREFETCH_LATE 1
+#endif
+constexpr int kEarlyRel = PBL_POOL_EARLYREL;
+constexpr uint32_t kPrefetch = PBL_POOL_PREFETCH;
 constexpr int kNW = PBL_POOL_WAVES;      // waves per workgroup (one workgroup per CU)
 constexpr int kNS = PBL_POOL_STAGES;     // staging buffers per workgroup
 constexpr int kTPBP = kNW * kWave;
@@ -914,13 +941,33 @@ __device__ __forceinline__ uint32_t acquire(PoolLds<kHide>& L) {
   return __builtin_amdgcn_readfirstlane(__shfl(s, 0, kWave));
 }
 
-// Return stage s to the pool once every LDS read of it has completed.
+// Take a free stage if there is one: one read of the mask and one fetch_and,
+// no spin and no sleep (the prefetch of a wave whose emit is unfinished must
+// never wait for a stage).  Returns the stage, or -1.  The priority stays the
+// emit's.
 template <bool kHide>
-__device__ __forceinline__ void release(PoolLds<kHide>& L, uint32_t s) {
+__device__ __forceinline__ int32_t try_acquire(PoolLds<kHide>& L) {
+  int32_t s = -1;
+  if (lane_id() == 0) {
+    const uint32_t m = __hip_atomic_load(&L.free_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (m) {
+      const uint32_t c = uint32_t(__builtin_ctz(m));
+      const uint32_t old =
+          __hip_atomic_fetch_and(&L.free_mask, ~(1u << c), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (old & (1u << c)) s = int32_t(c);
+    }
+  }
+  return __builtin_amdgcn_readfirstlane(__shfl(s, 0, kWave));
+}
+
+// Return stage s to the pool once every LDS read of it has completed.
+// `drop_prio`: the wave's issue priority falls back to the emit's.
+template <bool kHide>
+__device__ __forceinline__ void release(PoolLds<kHide>& L, uint32_t s, bool drop_prio = true) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   wave_sync();
   if (lane_id() == 0) __hip_atomic_fetch_or(&L.free_mask, 1u << s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-  if (PBL_POOL_PRIO) __builtin_amdgcn_s_setprio(0);
+  if (PBL_POOL_PRIO && drop_prio) __builtin_amdgcn_s_setprio(0);
 }
 
 // The block [boff, boff + blen) into stage S by LDS-DMA (granule g of the 16-B
@@ -1029,9 +1076,11 @@ struct Pend {
 // return).  The block's aggregate is always published before return, so every
 // later ticket can resolve past it while this wave goes on.  Blocks off the
 // fast path are finished here (live = false).
+// `staged`: the block's DMA into the stage was issued by the prefetch of the
+// emit before (still to be waited for).
 template <bool kHide>
 __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint32_t b, uint64_t boff, uint32_t blen,
-                                            Slot<kHide>& W, const Args& A) {
+                                            bool staged, Slot<kHide>& W, const Args& A) {
   Stage& S = L.st[s];
   const int l = lane_id();
   const uint32_t nb = A.in.n_blocks, flags = A.in.flags;
@@ -1052,7 +1101,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
     return P;
   }
   PSTAMP(A, b, 1, l == 0);
-  stage_dma(S, A.in.blocks, boff, blen);
+  if (!staged) stage_dma(S, A.in.blocks, boff, blen);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   wave_sync();
   PSTAMP(A, b, 2, l == 0);
@@ -1061,7 +1110,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
   uint32_t status = init_checks(LdsBlk{V}, blen, flags, &roff, &nres);
   bool slow = status == PBL_OK && nres > kKv;
   uint32_t nkv = 0, tkb = 0, tvb = 0;
-  bool published = false;
+  bool published = false, released = false;
   if (status == PBL_OK && !slow && roff > 0) {
     // lane l owns runs [r0, r1): contiguous, so a lane scan orders them
     const uint32_t R = (nres + kWave - 1) / kWave;
@@ -1088,6 +1137,15 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
       lb_publish(lb_state, nb, b, agg);
       published = true;
       PSTAMP(A, b, 3, l == 0);
+      // Without value prefixes, with every run inside the parked registers,
+      // the metadata pass reads the registers only (entry_meta touches V under
+      // setv alone, and setv needs the value-prefix flag): the stage goes back
+      // to the pool now.  (slow is false here, so this is the block's one release.)
+      if (kEarlyRel && single && !vprefix && !__ballot(over)) {
+        release(L, s, kEarlyRel != 2);
+        released = true;
+        PSTAMP(A, b, 9, l == 0);
+      }
       MState M{ie - (kHide ? acc.ne : acc.cnt), ic - acc.cnt, iv - acc.vb, 0, 0, 0};
       meta_runs<kHide>(W, V, r0, r1, nres, roff, flags, vprefix, single, over, RB, M);
       if (l < 5) W.vp[nkv + l] = tvb;
@@ -1097,9 +1155,15 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
   if (status == PBL_OK && slow) {
     block_slow(S, reinterpret_cast<uint8_t*>(W.m0), uint32_t(sizeof(W.m0)), A, b, boff, blen);
     release(L, s);
+    PSTAMP(A, b, 9, l == 0);
     return P;
   }
-  release(L, s);
+  if (!released) {
+    release(L, s);
+    PSTAMP(A, b, 9, l == 0);
+  } else if (PBL_POOL_PRIO && kEarlyRel == 2) {
+    __builtin_amdgcn_s_setprio(0);
+  }
   if (!published) {  // a failed or empty block: its (zero) aggregate
     const bool okb = status == PBL_OK;
     const uint64_t agg[kNumComp] = {okb ? nkv : 0, okb ? tkb : 0, okb ? tvb : 0, okb ? nres : 0};
@@ -1116,9 +1180,48 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
   return P;
 }
 
-// Resolve block P's look-back and write its outputs from slot W.
+// What a wave's emit hands to its next loop iteration: a stage and a ticket
+// taken ahead and whether the block's DMA is in flight.
+// kNextDone: the ticket was past the end of the batch (the stage went straight
+// back): the wave has no more blocks.
+struct Next {
+  uint32_t t, w;  // the ticket's block; stage | kNext* flags
+};
+constexpr uint32_t kNextHave = 4, kNextStaged = 8, kNextDone = 16;
+static_assert(kNS <= 4, "Next::w keeps the stage in two bits");
+
+// The prefetch: try to take a stage; with one in hand take the wave's next
+// ticket, read its descriptor and start the block's DMA into the stage.  Never
+// waits on anything but the wave's own memory operations.  Only the Stage is
+// filled: the wave's slot stays the current block's until its emit returns.
 template <bool kHide>
-__device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, const Args& A) {
+__device__ __forceinline__ void prefetch(PoolLds<kHide>& L, const Args& A, const uint32_t* ids, uint32_t nt, Next& X) {
+  const int32_t s = try_acquire(L);
+  if (s < 0) return;  // no stage free: the next loop iteration acquires one
+  uint32_t t = 0;
+  if (lane_id() == 0) t = g_atomic_add(reinterpret_cast<uint32_t*>(A.out.workspace), 1u);
+  t = __builtin_amdgcn_readfirstlane(__shfl(t, 0, kWave));
+  if (t >= nt) {
+    release(L, uint32_t(s));
+    X.w = kNextDone;
+    return;
+  }
+  if (ids) t = __builtin_amdgcn_readfirstlane(to_glb(ids)[t]);
+  const uint64_t boff = to_glb(A.in.block_off)[t];
+  const uint32_t blen = to_glb(A.in.block_len)[t];
+  // (a block past the stage is handed on as it is: block_big lets the stage go first)
+  const bool staged = blen <= kMaxFastLen;
+  X.t = t;
+  X.w = uint32_t(s) | kNextHave | (staged ? kNextStaged : 0u);
+  if (staged) stage_dma(L.st[s], A.in.blocks, boff, blen);
+  PSTAMP(A, t, 10, lane_id() == 0);
+}
+
+// Resolve block P's look-back and write its outputs from slot W.  `X`: the
+// wave's next block, staged under the last steps (kPrefetch).
+template <bool kHide>
+__device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, const Args& A, PoolLds<kHide>& L,
+                                           const uint32_t* ids, uint32_t nt, Next& X) {
   const int l = lane_id();
   const uint32_t nb = A.in.n_blocks, flags = A.in.flags, b = P.b;
   const pbl_decode_out& O = A.out;
@@ -1165,11 +1268,19 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   if (kUni) {
     // keys and values of the same 64 KVs in one step: a line of the block is
     // fetched once for both
+    // the prefetch point: past lb_finish, so nothing from here to the wave's
+    // next publish waits on another wave; before the step's loads, so their
+    // vmcnt wait covers the DMA
+    bool pf = kPrefetch != 0;
     if (kVDepth == 1) {
       for (uint32_t j0 = 0; j0 <= nkv; j0 += kWave) {
         KBatch KN;
         VBatch VN;
         const bool more = j0 + kWave <= nkv;
+        if (pf && (nkv - j0) / kWave + PBL_POOL_PREFETCH_LATE <= kPrefetch) {
+          prefetch<kHide>(L, A, ids, nt, X);
+          pf = false;
+        }
         if (more) {
           key_load<kHide, GSrc>(W, KS, raw, j0 + kWave, nkv, KN);
           val_load(W.vp, gb, nkv, j0 + kWave, VN);
@@ -1184,6 +1295,10 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
       for (uint32_t j0 = 0; j0 <= nkv; j0 += kWave) {
         KBatch KN;
         VBatch VN;
+        if (pf && (nkv - j0) / kWave + PBL_POOL_PREFETCH_LATE <= kPrefetch) {
+          prefetch<kHide>(L, A, ids, nt, X);
+          pf = false;
+        }
         if (j0 + kWave <= nkv) key_load<kHide, GSrc>(W, KS, raw, j0 + kWave, nkv, KN);
         if (j0 + 2 * kWave < nkv) val_load(W.vp, gb, nkv, j0 + 2 * kWave, VN);
         key_store<kHide, GSrc>(W, KS, A, b, j0, nkv, kvb, kbb, K, kcar);
@@ -1217,11 +1332,24 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
 
 // The persistent kernel: one workgroup of kNW waves per CU, each wave a loop
 // of (acquire a stage, take a ticket, stage / walk / describe the block into
-// one slot, then emit the block before it from the other slot).
-// Deadlock-free for any residency: a wave takes a ticket only while holding a
-// stage, publishes the block's aggregate before it lets the stage go, and
-// waits (in the look-back) only on smaller tickets, each held by a wave that
-// holds a stage or has published.
+// its slot, let the stage go, emit the block from the slot).  With
+// PBL_POOL_PREFETCH the acquire, the ticket and the DMA of the wave's next
+// block are done under the last steps of its emit (prefetch) and handed to
+// the next iteration in `Next`.
+// Deadlock-free for any residency:
+//  - a wave takes a ticket only while holding a stage (acquire, then ticket;
+//    the prefetch too), and publishes the block's aggregate before it lets
+//    that stage go;
+//  - between taking a ticket and publishing its aggregate a wave waits on
+//    nothing but its own memory operations: in the loop that is the DMA and
+//    the walk; after a prefetch it is the rest of the current emit, which has
+//    no look-back left (the prefetch point is past lb_finish) and no wait on
+//    another wave, and then the same DMA wait and walk;
+//  - the prefetch's try_acquire never blocks, so a wave with an unfinished
+//    emit never waits for a stage: every stage holder runs on to its publish
+//    and its release without needing any other wave to move;
+//  - the look-back waits only on smaller tickets, each held by a wave that
+//    holds a stage (and so reaches its publish by the above) or has published.
 // `ids` (mixed batches): the ascending ids of the batch's row blocks, their
 // count at workspace header word kWsRowCount; the colblk blocks' aggregates are
 // published before this launch (mixed_col_size_kernel), so the look-back walks
@@ -1236,28 +1364,42 @@ __global__ void __launch_bounds__(kTPBP, 1) rowblk_pool_kernel(Args A, const uin
   uint32_t* tick = reinterpret_cast<uint32_t*>(A.out.workspace);
   const uint32_t nt = ids ? __hip_atomic_load(to_glb(tick) + kWsRowCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                           : nb;
+  Next X{0, 0};
   for (;;) {
 #ifdef PBL_STAMPS
-    const uint64_t t_acq = __builtin_amdgcn_s_memtime();
+    const uint64_t t_acq = __builtin_amdgcn_s_memtime();  // (the end of the emit before)
 #endif
-    const uint32_t s = acquire(L);
-    uint32_t t0 = 0;
-    if (lane_id() == 0) t0 = g_atomic_add(tick, 1u);
-    t0 = __builtin_amdgcn_readfirstlane(__shfl(t0, 0, kWave));
-    if (t0 >= nt) {
-      release(L, s);
-      break;
+    uint32_t s, t0;
+    bool staged = false;
+    if (kPrefetch && (X.w & kNextDone)) break;
+    if (kPrefetch && (X.w & kNextHave)) {
+      // the emit before took the stage and the ticket and started the DMA
+      // (the descriptor is read again: two words, cache-hot, under the DMA)
+      s = X.w & 3u;
+      t0 = X.t;
+      staged = (X.w & kNextStaged) != 0;
+      X.w = 0;
+      if (PBL_POOL_PRIO) __builtin_amdgcn_s_setprio(PBL_POOL_PRIO);
+    } else {
+      s = acquire(L);
+      t0 = 0;
+      if (lane_id() == 0) t0 = g_atomic_add(tick, 1u);
+      t0 = __builtin_amdgcn_readfirstlane(__shfl(t0, 0, kWave));
+      if (t0 >= nt) {
+        release(L, s);
+        break;
+      }
+      if (ids) t0 = __builtin_amdgcn_readfirstlane(to_glb(ids)[t0]);
+      PSTAMP(A, t0, 0, lane_id() == 0);
     }
-    if (ids) t0 = __builtin_amdgcn_readfirstlane(to_glb(ids)[t0]);
-    PSTAMP(A, t0, 0, lane_id() == 0);
+    const uint64_t boff = to_glb(A.in.block_off)[t0];
+    const uint32_t blen = to_glb(A.in.block_len)[t0];
 #ifdef PBL_STAMPS
     if (lane_id() == 0)
       reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(A.out.workspace) + ws_bytes(nb))[uint64_t(t0) * 16 + 8] = t_acq;
 #endif
-    const uint64_t boff = to_glb(A.in.block_off)[t0];
-    const uint32_t blen = to_glb(A.in.block_len)[t0];
-    const Pend Q = block_front<kHide>(L, s, t0, boff, blen, W, A);
-    if (Q.live) block_emit<kHide>(Q, W, A);
+    const Pend Q = block_front<kHide>(L, s, t0, boff, blen, staged, W, A);
+    if (Q.live) block_emit<kHide>(Q, W, A, L, ids, nt, X);
     wave_sync();  // (the slot is the next block's)
   }
 }
