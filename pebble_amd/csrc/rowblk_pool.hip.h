@@ -32,7 +32,13 @@
 //               keys    lane per KV: offsets (a wave scan of the key lengths),
 //                       trailer, flags, entry offset, the user key merged from
 //                       its prefix chain
-//               values  8 lanes per KV, 16-B chunks
+//               values  8 lanes per KV, 16-B chunks; a step whose values are
+//                       all empty or 16..128 B long is the fast step
+//                       (PBL_POOL_VFAST): descriptors read once, lane per
+//                       KV, permuted to the groups, no per-KV branch
+//             (PBL_POOL_SBASE, off by default: measured no gain, DESIGN.md
+//             3.1) the step's uniform bases in SGPRs, lane offsets unsigned
+//             32-bit
 //
 // LDS per CU: 3 stages x 32.8 KB + 8 slots x ~8 KB (one per wave).
 //
@@ -175,9 +181,62 @@ __device__ __forceinline__ void st_out(gptr<T> p, T v) {
 #endif
 }
 
-// Bytes [0, n) of w (n <= 16) to p, any alignment: one 16-B store when whole,
-// else the fewest 8/4/2/1-B stores (nothing past n: the next key belongs to
-// another lane).
+// PBL_POOL_SBASE: the emit's global accesses address a wave-uniform base held
+// in SGPRs plus an unsigned 32-bit lane offset (global_load / global_store
+// "v_off, s[base:base+1]": no 64-bit address pair built per access).  The
+// block's exclusive bases and source pointer go through readfirstlane once.
+#ifndef PBL_POOL_SBASE
+#define PBL_POOL_SBASE 0  // compiled out: no gain alone or on top of the other two
+#endif
+// PBL_POOL_VFAST: an emit step whose 64 values are all empty or 16..128 B
+// long copies them as straight-line code, the descriptors read from the slot
+// once, lane per KV, and handed to the 8-lane groups by cross-lane permutes.
+#ifndef PBL_POOL_VFAST
+#define PBL_POOL_VFAST 1
+#endif
+constexpr bool kSBase = PBL_POOL_SBASE != 0;
+constexpr bool kVFast = PBL_POOL_VFAST != 0;
+
+// A wave-uniform value / pointer moved to SGPRs (kOn false: as it is).
+template <bool kOn>
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+  if (!kOn) return v;
+  return uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v))))) |
+         uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v >> 32))))) << 32;
+}
+template <bool kOn, class T>
+__device__ __forceinline__ gptr<T> ubase(gptr<T> p) {
+  return (gptr<T>)uni64<kOn>((uint64_t)p);
+}
+
+// Bytes [0, n) of w (n <= 16) to b + off, any alignment: one 16-B store when
+// whole, else the fewest 8/4/2/1-B stores (nothing past n: the next key
+// belongs to another lane).
+__device__ __forceinline__ void store_n(gptr<uint8_t> b, uint32_t off, const uint4& w, uint32_t n) {
+  if (n == 16) {
+    st_out((gptr<u32x4_ug>)(b + off), u32x4_ug{w.x, w.y, w.z, w.w});
+    return;
+  }
+  uint64_t lo = uint64_t(w.x) | uint64_t(w.y) << 32, hi = uint64_t(w.z) | uint64_t(w.w) << 32;
+  uint32_t o = off;
+  if (n & 8) {
+    st_out((gptr<u64_ug>)(b + o), u64_ug(lo));
+    lo = hi;
+    o += 8;
+  }
+  if (n & 4) {
+    st_out((gptr<u32_ug>)(b + o), u32_ug(lo));
+    lo >>= 32;
+    o += 4;
+  }
+  if (n & 2) {
+    st_out((gptr<u16_ug>)(b + o), u16_ug(lo));
+    lo >>= 16;
+    o += 2;
+  }
+  if (n & 1) st_out(b + o, uint8_t(lo));
+}
+
 __device__ __forceinline__ void store_n(gptr<uint8_t> p, const uint4& w, uint32_t n) {
   if (n == 16) {
     st_out((gptr<u32x4_ug>)p, u32x4_ug{w.x, w.y, w.z, w.w});
@@ -209,7 +268,7 @@ __device__ __forceinline__ void store_n(gptr<uint8_t> p, const uint4& w, uint32_
 // two edges the general path's aligned pair (never a byte outside them).
 __device__ __forceinline__ uint4 gld16(gptr<const uint8_t> g, int32_t i, uint32_t blen, uint32_t end16) {
   if (i >= 0 && uint32_t(i) + 16u <= end16) {
-    const u32x4 v = *(gptr<const u32x4_ug>)(g + i);
+    const u32x4 v = *(gptr<const u32x4_ug>)(g + uint32_t(i));
     return make_uint4(v.x, v.y, v.z, v.w);
   }
   return GlbBlk{g, blen}.ld16(i);
@@ -582,6 +641,37 @@ __device__ __forceinline__ bool key_fast(uint64_t m, uint64_t mp, bool raw) {
   return ukl_of(m, raw) <= 16 && (sh == 0 || m_sh(mp) == 0) && (raw || kl < 8 || kl - 8 >= sh);
 }
 
+// PBL_POOL_KWIN: a key is on the fast form only if its 16-B windows lie inside
+// the block's 16-B granules, so key_load issues plain loads and nothing else:
+// the edge form of GSrc::ld16 (an aligned pair merged after a vmcnt wait) inside
+// it made the compiler drain every memory operation in flight, the previous
+// step's stores included, between a step's key loads and its value loads.  A
+// key at the block's edge takes the general form (same bytes, loaded at its
+// stores).  Sources without edges (the stage in LDS): as before.
+#ifndef PBL_POOL_KWIN
+#define PBL_POOL_KWIN 1
+#endif
+constexpr bool kKWin = PBL_POOL_KWIN != 0;
+template <class Src>
+__device__ __forceinline__ bool win_in(const Src&, int32_t) { return true; }
+__device__ __forceinline__ bool win_in(const GSrc& V, int32_t i) {
+  return !kKWin || (i >= 0 && uint32_t(i) + 16u <= V.end16);
+}
+template <class Src>
+__device__ __forceinline__ uint4 ld16_in(const Src& V, int32_t i) { return V.ld16(i); }
+__device__ __forceinline__ uint4 ld16_in(const GSrc& V, int32_t i) {
+  if (!kKWin) return V.ld16(i);
+  const u32x4 v = *(gptr<const u32x4_ug>)(V.g + uint32_t(i));
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+template <class Src>
+__device__ __forceinline__ bool key_fast_at(const Src& V, uint64_t m, uint64_t mp, bool raw) {
+  const uint32_t sh = m_sh(m);
+  return key_fast(m, mp, raw) &&
+         (ukl_of(m, raw) == 0 ||
+          (win_in(V, int32_t(m_ksrc(m)) - int32_t(sh)) && (sh == 0 || win_in(V, int32_t(m_ksrc(mp))))));
+}
+
 template <bool kHide, class Src>
 __device__ __forceinline__ void key_load(const Slot<kHide>& W, const Src& V, bool raw, uint32_t j0, uint32_t nkv,
                                          KBatch& K) {
@@ -601,11 +691,11 @@ __device__ __forceinline__ void key_load(const Slot<kHide>& W, const Src& V, boo
     const uint32_t j = j0 + kWave * u + l;
     const uint64_t m = Km[u];
     const uint32_t kl = m_klen(m), sh = m_sh(m), ukl = ukl_of(m, raw);
-    const bool fast = j < nkv && key_fast(m, Kmp[u], raw);
+    const bool fast = j < nkv && key_fast_at(V, m, Kmp[u], raw);
     K.tr[u] = 0;
     if (fast && !raw && kl >= 8) K.tr[u] = V.ld8(m_ksrc(m) + (kl - 8 - sh));
-    if (fast && ukl) K.ka[u] = V.ld16(int32_t(m_ksrc(m)) - int32_t(sh));
-    if (fast && ukl && sh) K.kp[u] = V.ld16(int32_t(m_ksrc(Kmp[u])));
+    if (fast && ukl) K.ka[u] = ld16_in(V, int32_t(m_ksrc(m)) - int32_t(sh));
+    if (fast && ukl && sh) K.kp[u] = ld16_in(V, int32_t(m_ksrc(Kmp[u])));
   }
 }
 
@@ -624,15 +714,17 @@ __device__ __forceinline__ void key_load(const Slot<kHide>& W, const Src& V, boo
 #endif
 constexpr uint32_t kWaveKey = PBL_POOL_WAVEKEY;
 __device__ __forceinline__ bool wave_key(uint32_t ukl, uint32_t sh) { return ukl > kWaveKey && ukl >= sh + 16; }
-template <class Src>
+template <bool kOff, class Src>
 __device__ __forceinline__ void store_key_general(const uint64_t* M0, const Src& V, uint64_t m, uint32_t ukl,
-                                                  gptr<uint8_t> dst) {
+                                                  gptr<uint8_t> kbytes, uint32_t ko) {
+  const gptr<uint8_t> dst = kbytes + ko;
   const uint32_t sh = m_sh(m);
   const int32_t own = int32_t(m_ksrc(m)) - int32_t(sh);  // block offset of key byte 0 in the entry's bytes
   uint32_t c = 0;
   for (; c < ukl && c < sh; c += 16) {
     const uint32_t n = ukl - c < 16 ? ukl - c : 16u;
-    store_n(dst + c, key_chunk(M0, V, m, c, n), n);
+    if (kOff) store_n(kbytes, ko + c, key_chunk(M0, V, m, c, n), n);
+    else store_n(dst + c, key_chunk(M0, V, m, c, n), n);
   }
   if (wave_key(ukl, sh)) return;
   for (; c < ukl; c += 16 * PBL_POOL_KOWN) {
@@ -645,7 +737,10 @@ __device__ __forceinline__ void store_key_general(const uint64_t* M0, const Src&
 #pragma unroll
     for (int k = 0; k < PBL_POOL_KOWN; k++) {
       const uint32_t cc = c + 16 * k;
-      if (cc < ukl) store_n(dst + cc, w[k], ukl - cc < 16 ? ukl - cc : 16u);
+      if (cc < ukl) {
+        if (kOff) store_n(kbytes, ko + cc, w[k], ukl - cc < 16 ? ukl - cc : 16u);
+        else store_n(dst + cc, w[k], ukl - cc < 16 ? ukl - cc : 16u);
+      }
     }
   }
 }
@@ -654,13 +749,26 @@ __device__ __forceinline__ void store_key_general(const uint64_t* M0, const Src&
 // key lengths per u, `kcar` carrying the running total (KV nkv gets the total).
 // kPart (the two-pass row emit splits the stores over two waves): 0 all, 1 all
 // but the long keys' own bytes, 2 only those (K unused).
-template <bool kHide, class Src, int kPart = 0>
+// kOff (the pool kernel's emit): every store addresses the batch's base of
+// its array plus the lane's unsigned 32-bit offset (the caller's b, j0, kvb and
+// kbb are wave-uniform), the bases in SGPRs with PBL_POOL_SBASE.  kVo: the
+// KVs' value offsets come in `vo` (the caller's one read of vp), kKU == 1.
+template <bool kHide, class Src, int kPart = 0, bool kOff = false, bool kVo = false>
 __device__ __forceinline__ void key_store(const Slot<kHide>& W, const Src& V, const Args& A, uint32_t b, uint32_t j0,
-                                          uint32_t nkv, uint64_t kvb, uint64_t kbb, const KBatch& K, uint32_t& kcar) {
+                                          uint32_t nkv, uint64_t kvb, uint64_t kbb, const KBatch& K, uint32_t& kcar,
+                                          uint32_t vo = 0) {
+  static_assert(!kVo || kKU == 1, "one value offset per lane");
   const int l = lane_id();
   const uint32_t flags = A.in.flags;
   const pbl_decode_out& O = A.out;
-  const gptr<uint8_t> kbytes = to_glb(O.key_bytes) + kbb;
+  constexpr bool kSB = kOff && kSBase;
+  const gptr<uint8_t> kbytes = ubase<kSB>(to_glb(O.key_bytes) + kbb);
+  // the batch's first element of every per-KV array
+  const gptr<uint32_t> p_koff = ubase<kSB>(to_glb(O.key_off) + (kvb + b + j0));
+  const gptr<uint32_t> p_voff = ubase<kSB>(to_glb(O.val_off) + (kvb + b + j0));
+  const gptr<uint64_t> p_tr = ubase<kSB>(to_glb(O.trailer) + (kvb + j0));
+  const gptr<uint8_t> p_fl = ubase<kSB>(to_glb(O.kv_flags) + (kvb + j0));
+  const gptr<uint32_t> p_eo = ubase<kSB>(to_glb(O.entry_off) + (kvb + j0));
   const bool raw = (flags & PBL_ROW_RAW_KEYS) != 0;
   uint32_t kc0[kKU];
   uint64_t Km[kKU], Kmp[kKU];
@@ -677,7 +785,7 @@ __device__ __forceinline__ void key_store(const Slot<kHide>& W, const Src& V, co
   }
 #pragma unroll
   for (int u = 0; u < kKU; u++) {
-    const uint32_t j = j0 + kWave * u + l;
+    const uint32_t lj = uint32_t(kWave * u + l), j = j0 + lj;
     const uint64_t m = Km[u];
     const uint32_t ukl = j < nkv ? ukl_of(m, raw) : 0u;
     const uint32_t incl = dpp_incl_scan(ukl);
@@ -685,16 +793,21 @@ __device__ __forceinline__ void key_store(const Slot<kHide>& W, const Src& V, co
     const uint32_t ko = kcar + incl - ukl;
     kcar += last_lane(incl);
     if (kPart == 2 || j > nkv) continue;
-    st_out(to_glb(O.key_off) + (kvb + b + j), ko);
-    st_out(to_glb(O.val_off) + (kvb + b + j), uint32_t(W.vp[j] & 0xffffu));
+    if (kOff) {
+      st_out(p_koff + lj, ko);
+      st_out(p_voff + lj, kVo ? vo : uint32_t(W.vp[j] & 0xffffu));
+    } else {
+      st_out(to_glb(O.key_off) + (kvb + b + j), ko);
+      st_out(to_glb(O.val_off) + (kvb + b + j), uint32_t(W.vp[j] & 0xffffu));
+    }
     if (j == nkv) continue;
     const uint32_t kl = m_klen(m), sh = m_sh(m);
     uint64_t t;
     uint32_t f = m_fl(m);
-    if (!key_fast(m, Kmp[u], raw)) {
+    if (!key_fast_at(V, m, Kmp[u], raw)) {
       const uint32_t e = kHide ? uint32_t(W.ent[j]) : j;
       t = trailer_of(W.m0, V, int(e), m, &f, flags);
-      store_key_general(W.m0, V, m, ukl, kbytes + ko);
+      store_key_general<kOff>(W.m0, V, m, ukl, kbytes, ko);
     } else {
       uint64_t tukl;
       split_trailer(K.tr[u], kl, flags, &t, &tukl, &f);
@@ -706,12 +819,19 @@ __device__ __forceinline__ void key_store(const Slot<kHide>& W, const Src& V, co
           merge16(w, K.ka[u], lo, ukl);
           merge16(w, K.kp[u], 0, lo);
         }
-        store_n(kbytes + ko, w, ukl);
+        if (kOff) store_n(kbytes, ko, w, ukl);
+        else store_n(kbytes + ko, w, ukl);
       }
     }
-    st_out(to_glb(O.trailer) + (kvb + j), uint64_t(with_seq(t, A.in.synthetic_seq_num, flags)));
-    if (O.kv_flags) st_out(to_glb(O.kv_flags) + (kvb + j), uint8_t(f));
-    if (O.entry_off) st_out(to_glb(O.entry_off) + (kvb + j), uint32_t(m_ksrc(m) - m_hl(m)));
+    if (kOff) {
+      st_out(p_tr + lj, uint64_t(with_seq(t, A.in.synthetic_seq_num, flags)));
+      if (O.kv_flags) st_out(p_fl + lj, uint8_t(f));
+      if (O.entry_off) st_out(p_eo + lj, uint32_t(m_ksrc(m) - m_hl(m)));
+    } else {
+      st_out(to_glb(O.trailer) + (kvb + j), uint64_t(with_seq(t, A.in.synthetic_seq_num, flags)));
+      if (O.kv_flags) st_out(to_glb(O.kv_flags) + (kvb + j), uint8_t(f));
+      if (O.entry_off) st_out(to_glb(O.entry_off) + (kvb + j), uint32_t(m_ksrc(m) - m_hl(m)));
+    }
   }
   if (kPart == 1) return;
   // the own bytes [shared, ukl) of long keys: one contiguous range of the
@@ -827,6 +947,63 @@ __device__ __forceinline__ void val_store(const uint32_t* vp, uint32_t nkv, uint
     } else if (S.vl < 16) {
       for (uint32_t o = c; o < S.vl; o += 8) vbytes[S.vo + o] = g[S.vs + o];
     }
+  }
+}
+
+// ---- the fast value step (PBL_POOL_VFAST) --------------------------------------
+// The descriptors of a step's 64 KVs, read from the slot once, lane per KV
+// (the index clamped to nkv: vp[nkv .. nkv + 4] hold the total, so a lane past
+// the last KV sees an empty value at the end): the value's length above its
+// source offset (lw, for the loads) and above its output offset (sw, for the
+// stores and for val_off).  All three fields fit 16 bits (blocks <= 32 KiB).
+// `fast`: every value of the step is empty or 16 .. 128 B long, one chunk per
+// lane of its group and no byte loop.
+struct VDesc {
+  uint32_t lw, sw;
+  bool fast;
+};
+__device__ __forceinline__ VDesc val_desc(const uint32_t* vp, uint32_t nkv, uint32_t j0) {
+  const uint32_t j = min(j0 + uint32_t(lane_id()), nkv);
+  const uint32_t a = vp[j], z = vp[j + 1];
+  const uint32_t vo = a & 0xffffu, vl = (z & 0xffffu) - vo;
+  VDesc D;
+  D.lw = (a >> 16) | vl << 16;
+  D.sw = vo | vl << 16;
+  D.fast = __ballot(vl != 0 && vl - 16u > 112u) == 0;
+  return D;
+}
+// KV 8 u + lane / 8 of the step is group lane / 8's u-th: its word from the
+// lane that read it (every lane reads: the caller's branch is wave-uniform).
+__device__ __forceinline__ uint32_t grp_word(uint32_t w, int u) {
+  return uint32_t(__builtin_amdgcn_ds_bpermute(int(4u * (8u * uint32_t(u) + (uint32_t(lane_id()) >> 3))), int(w)));
+}
+// A lane's chunk of a fast step's value of length vl at offset `at`: the
+// offset of its 16 bytes (the last chunk ends at the value's end), or kNoChunk.
+constexpr uint32_t kNoChunk = ~0u;
+__device__ __forceinline__ uint32_t fast_chunk(uint32_t w) {
+  const uint32_t c16 = 16u * (uint32_t(lane_id()) & 7u), at = w & 0xffffu, vl = w >> 16;
+  return c16 < vl ? at + min(c16, vl - 16u) : kNoChunk;
+}
+// The loads of a fast step.  g16: the block's pointer aligned down to 16 B,
+// ph: the block's first byte in it; a lane with no chunk loads granule 0.
+__device__ __forceinline__ void val_load_fast(gptr<const uint8_t> g16, uint32_t ph, uint32_t lw, VBatch& B) {
+  uint32_t w[kVG];
+#pragma unroll
+  for (int u = 0; u < kVG; u++) w[u] = grp_word(lw, u);
+#pragma unroll
+  for (int u = 0; u < kVG; u++) {
+    const uint32_t o = fast_chunk(w[u]);
+    B.x[u] = *(gptr<const u32x4_ug>)(g16 + (o != kNoChunk ? ph + o : 0u));
+  }
+}
+__device__ __forceinline__ void val_store_fast(uint32_t sw, const VBatch& B, gptr<uint8_t> vbytes) {
+  uint32_t w[kVG];
+#pragma unroll
+  for (int u = 0; u < kVG; u++) w[u] = grp_word(sw, u);
+#pragma unroll
+  for (int u = 0; u < kVG; u++) {
+    const uint32_t o = fast_chunk(w[u]);
+    if (o != kNoChunk) st_out((gptr<u32x4_ug>)(vbytes + o), u32x4_ug(B.x[u]));
   }
 }
 
@@ -1227,7 +1404,11 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   const pbl_decode_out& O = A.out;
   uint64_t* lb_state = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(O.workspace) + kWsHeader);
   const uint8_t* gblk = A.in.blocks + P.boff;
-  const gptr<const uint8_t> gb = to_glb(gblk);
+  const gptr<const uint8_t> gb = ubase<kSBase>(to_glb(gblk));
+  // (the fast value step's loads: the block's first 16-B granule and the block's phase in it)
+  const uint32_t ph = uint32_t(uint64_t(gblk) & 15u);
+  const gptr<const uint8_t> g16 = ubase<kSBase>(to_glb(gblk - ph));
+  constexpr bool kFastSteps = kVFast && kUni && kVDepth == 1;
   const GSrc KS{gb, P.blen, uint32_t(((uint64_t(gblk) + P.blen + 15) & ~uint64_t(15)) - uint64_t(gblk))};
   const bool raw = (flags & PBL_ROW_RAW_KEYS) != 0;
   const uint32_t nkv = P.nkv, nres = P.nres;
@@ -1237,11 +1418,14 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   if (b > 0) G.issue(LbPtrs(lb_state, nb), int64_t(b) - 1);
   KBatch K;
   VBatch VB, VB1;
+  VDesc VD{0, 0, true};
   uint32_t rs0 = 0;
   const bool ok0 = P.status == PBL_OK;
   if (ok0) {
     key_load<kHide, GSrc>(W, KS, raw, 0, nkv, K);
-    val_load(W.vp, gb, nkv, 0, VB);
+    if (kFastSteps) VD = val_desc(W.vp, nkv, 0);
+    if (kFastSteps && VD.fast) val_load_fast(g16, ph, VD.lw, VB);
+    else val_load(W.vp, gb, nkv, 0, VB);
     if (kVDepth == 2) val_load(W.vp, gb, nkv, 8 * kVG, VB1);
     if (O.restarts && uint32_t(l) < nres) rs0 = KS.le32(P.roff + 4 * l);
   }
@@ -1261,10 +1445,12 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   if (status != PBL_OK) return;
 
   // ---- keys and per-KV arrays: lane per KV ------------------------------------
-  const uint64_t kvb = excl[0], kbb = excl[1], vbb = excl[2], rbb = excl[3];
-  if (O.restarts && uint32_t(l) < nres) to_glb(O.restarts)[rbb + l] = rs0;
+  const uint64_t kvb = uni64<kSBase>(excl[0]), kbb = uni64<kSBase>(excl[1]), vbb = uni64<kSBase>(excl[2]),
+                 rbb = uni64<kSBase>(excl[3]);
+  const gptr<uint32_t> p_rst = ubase<kSBase>(to_glb(O.restarts) + rbb);
+  if (O.restarts && uint32_t(l) < nres) p_rst[uint32_t(l)] = rs0;
   uint32_t kcar = 0;
-  const gptr<uint8_t> vbytes = to_glb(O.val_bytes) + vbb;
+  const gptr<uint8_t> vbytes = ubase<kSBase>(to_glb(O.val_bytes) + vbb);
   if (kUni) {
     // keys and values of the same 64 KVs in one step: a line of the block is
     // fetched once for both
@@ -1272,7 +1458,32 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
     // next publish waits on another wave; before the step's loads, so their
     // vmcnt wait covers the DMA
     bool pf = kPrefetch != 0;
-    if (kVDepth == 1) {
+    if (kFastSteps) {
+      // a step's class (VD.fast) is decided at its loads and carried, with its
+      // descriptors, to its stores one iteration later
+      for (uint32_t j0 = 0; j0 <= nkv; j0 += kWave) {
+        KBatch KN;
+        VBatch VN;
+        VDesc DN{0, 0, true};
+        const bool more = j0 + kWave <= nkv;
+        if (pf && (nkv - j0) / kWave + PBL_POOL_PREFETCH_LATE <= kPrefetch) {
+          prefetch<kHide>(L, A, ids, nt, X);
+          pf = false;
+        }
+        if (more) {
+          DN = val_desc(W.vp, nkv, j0 + kWave);
+          if (DN.fast) val_load_fast(g16, ph, DN.lw, VN);
+          else val_load(W.vp, gb, nkv, j0 + kWave, VN);
+          key_load<kHide, GSrc>(W, KS, raw, j0 + kWave, nkv, KN);
+        }
+        key_store<kHide, GSrc, 0, true, true>(W, KS, A, b, j0, nkv, kvb, kbb, K, kcar, VD.sw & 0xffffu);
+        if (VD.fast) val_store_fast(VD.sw, VB, vbytes);
+        else val_store(W.vp, nkv, j0, VB, gb, vbytes);
+        K = KN;
+        VB = VN;
+        VD = DN;
+      }
+    } else if (kVDepth == 1) {
       for (uint32_t j0 = 0; j0 <= nkv; j0 += kWave) {
         KBatch KN;
         VBatch VN;
@@ -1285,7 +1496,7 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
           key_load<kHide, GSrc>(W, KS, raw, j0 + kWave, nkv, KN);
           val_load(W.vp, gb, nkv, j0 + kWave, VN);
         }
-        key_store<kHide, GSrc>(W, KS, A, b, j0, nkv, kvb, kbb, K, kcar);
+        key_store<kHide, GSrc, 0, true>(W, KS, A, b, j0, nkv, kvb, kbb, K, kcar);
         val_store(W.vp, nkv, j0, VB, gb, vbytes);
         K = KN;
         VB = VN;
@@ -1309,7 +1520,7 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
       }
     }
     if (O.restarts)
-      for (uint32_t r = kWave + l; r < nres; r += kWave) to_glb(O.restarts)[rbb + r] = KS.le32(P.roff + 4 * r);
+      for (uint32_t r = kWave + l; r < nres; r += kWave) p_rst[r] = KS.le32(P.roff + 4 * r);
     copy_long_values(W.vp, gb, nkv, vbytes);
     PSTAMP(A, b, 6, l == 0);
     PSTAMP(A, b, 7, l == 0);
