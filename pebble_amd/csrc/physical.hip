@@ -325,116 +325,6 @@ struct SnapLds {
   uint4 dst4[(kSnapCap + 32) / 16];
 };
 
-typedef uint32_t su32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-struct LdsBytes {
-  lptr<uint8_t> p;
-  static constexpr bool kVec = true;
-  __device__ uint8_t operator[](uint32_t i) const { return p[i]; }
-  __device__ su32x4_u get16(uint32_t i) const { return *(lptr<const su32x4_u>)(p + i); }
-};
-struct LdsBytesW {
-  lptr<uint8_t> p;
-  __device__ uint8_t get(uint32_t i) const { return p[i]; }
-  __device__ void set(uint32_t i, uint8_t v) const { p[i] = v; }
-  __device__ su32x4_u get16(uint32_t i) const { return *(lptr<const su32x4_u>)(p + i); }
-  __device__ void set16(uint32_t i, su32x4_u v) const { *(lptr<su32x4_u>)(p + i) = v; }
-};
-struct GlbBytes {
-  gptr<const uint8_t> p;
-  static constexpr bool kVec = false;
-  __device__ uint8_t operator[](uint32_t i) const { return p[i]; }
-  __device__ su32x4_u get16(uint32_t) const { return su32x4_u{0, 0, 0, 0}; }
-};
-struct GlbBytesW {
-  gptr<uint8_t> p;
-  __device__ uint8_t get(uint32_t i) const { return p[i]; }
-  __device__ void set(uint32_t i, uint8_t v) const { p[i] = v; }
-};
-
-#include "minlz_dec.hip.h"
-
-// Decode one snappy block.  Lane 0 reads element headers; the wave copies.
-// Returns the decoded length, or ~0u when the input is corrupt.
-// (lane, step): the wave's lanes (lane_id(), 64) or one lane alone (0, 1).
-template <class Src, class Dst>
-__device__ inline uint32_t snappy_wave(Src src, uint32_t n, Dst dst, uint32_t cap, uint32_t lane, uint32_t step) {
-  uint32_t dlen = 0, s = 0;
-  bool ok = true;
-  {  // uvarint decoded length
-    uint64_t x = 0;
-    bool done = false;
-    for (uint32_t i = 0; i < n && i < 10 && !done; i++) {
-      x |= uint64_t(src[i] & 0x7f) << (7 * i);
-      if (src[i] < 0x80) {
-        done = true;
-        s = i + 1;
-      }
-    }
-    ok = done && x <= cap;
-    dlen = uint32_t(x);
-  }
-  uint32_t d = 0;
-  while (ok && s < n) {
-    // element header (every lane reads the same bytes: uniform control flow)
-    const uint32_t t = src[s];
-    uint32_t kind = t & 3, len = 0, off = 0, lit = 0;
-    if (kind == 0) {
-      uint32_t x = t >> 2;
-      if (x < 60) {
-        s += 1;
-      } else {
-        const uint32_t nb = x - 59;
-        if (s + 1 + nb > n) { ok = false; break; }
-        x = 0;
-        for (uint32_t i = 0; i < nb; i++) x |= uint32_t(src[s + 1 + i]) << (8 * i);
-        s += 1 + nb;
-      }
-      len = x + 1;
-      if (len > n - s || len > dlen - d) { ok = false; break; }
-      lit = s;
-      s += len;
-    } else if (kind == 1) {
-      if (s + 2 > n) { ok = false; break; }
-      len = 4 + ((t >> 2) & 7);
-      off = ((t & 0xe0) << 3) | src[s + 1];
-      s += 2;
-    } else if (kind == 2) {
-      if (s + 3 > n) { ok = false; break; }
-      len = 1 + (t >> 2);
-      off = uint32_t(src[s + 1]) | uint32_t(src[s + 2]) << 8;
-      s += 3;
-    } else {
-      if (s + 5 > n) { ok = false; break; }
-      len = 1 + (t >> 2);
-      off = uint32_t(src[s + 1]) | uint32_t(src[s + 2]) << 8 | uint32_t(src[s + 3]) << 16 | uint32_t(src[s + 4]) << 24;
-      s += 5;
-    }
-    if (kind != 0 && (off == 0 || off > d || len > dlen - d)) { ok = false; break; }
-    if constexpr (Src::kVec) {
-      // LDS -> LDS (the wave): 16 bytes per lane per step.  A chunk may write
-      // up to 15 bytes past the element's end: later elements rewrite them, and
-      // copies read only below d.  A copy whose offset is at least one step's
-      // span (64 x 16 B) never reads what the same step writes.
-      if (kind == 0) {
-        for (uint32_t i = 16 * lane; i < len; i += 16 * step) dst.set16(d + i, src.get16(lit + i));
-      } else if (off >= 16 * kWave) {
-        for (uint32_t i = 16 * lane; i < len; i += 16 * step) dst.set16(d + i, dst.get16(d - off + i));
-      } else {
-        for (uint32_t i = lane; i < len; i += step) dst.set(d + i, dst.get(d - off + (i % off)));
-      }
-    } else {
-      if (kind == 0) {
-        for (uint32_t i = lane; i < len; i += step) dst.set(d + i, src[lit + i]);
-      } else {
-        for (uint32_t i = lane; i < len; i += step) dst.set(d + i, dst.get(d - off + (i % off)));
-      }
-    }
-    wave_sync();
-    d += len;
-  }
-  return ok && d == dlen ? d : ~0u;
-}
-
 // ---- snappy: snappy2_kernel (also the path for blocks the walk does not cover) ----
 // One wave per block, four blocks per CU (38 KB of LDS each: the compressed
 // bytes and a queue of element descriptors; the output goes straight to HBM):
@@ -462,6 +352,22 @@ __device__ uint32_t g_sn_dummy;
 #define SN_ACC(i, v)
 #endif
 #include "snappy_dec.hip.h"
+
+struct LdsBytes {
+  lptr<uint8_t> p;
+  static constexpr bool kVec = true;
+  __device__ uint8_t operator[](uint32_t i) const { return p[i]; }
+  __device__ su32x4_u get16(uint32_t i) const { return *(lptr<const su32x4_u>)(p + i); }
+};
+struct LdsBytesW {
+  lptr<uint8_t> p;
+  __device__ uint8_t get(uint32_t i) const { return p[i]; }
+  __device__ void set(uint32_t i, uint8_t v) const { p[i] = v; }
+  __device__ su32x4_u get16(uint32_t i) const { return *(lptr<const su32x4_u>)(p + i); }
+  __device__ void set16(uint32_t i, su32x4_u v) const { *(lptr<su32x4_u>)(p + i) = v; }
+};
+
+#include "minlz_dec.hip.h"
 
 // The element walk of the blocks snappy4_kernel decodes, a lane per block.
 __global__ void __launch_bounds__(kTPB) snappy_walk_kernel(const pbl_phys_batch B, uint8_t* out,

@@ -1,5 +1,6 @@
-// snappy_dec.hip.h — the snappy block decoder of snappy2_kernel (physical.hip),
-// written against a small set of wave primitives (lptr / gptr, lane_id,
+// snappy_dec.hip.h — the snappy block decoders of physical.hip (snappy2_kernel's
+// LDS decoder sn_decode, snappy4_kernel's sn4_decode behind the walk, and the
+// one-lane global-memory decoder snappy_wave), written against a small set of wave primitives (lptr / gptr, lane_id,
 // wave_sync, __shfl, __ballot, readfirstlane, alignbyte) so that
 // scripts/snappy_emu.cpp can run the same code on the host with 64 threads in
 // lockstep.  Included by physical.hip inside namespace pbl::phys, after
@@ -719,4 +720,88 @@ __device__ bool sn4_decode(Snap4Lds& S, gptr<const uint8_t> src, uint32_t n, uin
 #endif
   }
   return d == D;
+}
+
+
+// ==== the global-memory route: blocks past the LDS stage or past 64 KiB ========
+// (GlbBytes / GlbBytesW also serve minlz_wave: kVec and get16 are its interface)
+typedef uint32_t su32x4_u __attribute__((ext_vector_type(4), aligned(1)));
+struct GlbBytes {
+  gptr<const uint8_t> p;
+  static constexpr bool kVec = false;
+  __device__ uint8_t operator[](uint32_t i) const { return p[i]; }
+  __device__ su32x4_u get16(uint32_t) const { return su32x4_u{0, 0, 0, 0}; }
+};
+struct GlbBytesW {
+  gptr<uint8_t> p;
+  __device__ uint8_t get(uint32_t i) const { return p[i]; }
+  __device__ void set(uint32_t i, uint8_t v) const { p[i] = v; }
+};
+
+// Decode one snappy block.  Lane 0 reads element headers; the wave copies.
+// Returns the decoded length, or ~0u when the input is corrupt.
+// (lane, step): the wave's lanes (lane_id(), 64) or one lane alone (0, 1).
+template <class Src, class Dst>
+__device__ inline uint32_t snappy_wave(Src src, uint32_t n, Dst dst, uint32_t cap, uint32_t lane, uint32_t step) {
+  uint32_t dlen = 0, s = 0;
+  bool ok = true;
+  {  // uvarint decoded length
+    uint64_t x = 0;
+    bool done = false;
+    for (uint32_t i = 0; i < n && i < 10 && !done; i++) {
+      x |= uint64_t(src[i] & 0x7f) << (7 * i);
+      if (src[i] < 0x80) {
+        done = true;
+        s = i + 1;
+      }
+    }
+    ok = done && x <= cap;
+    dlen = uint32_t(x);
+  }
+  uint32_t d = 0;
+  while (ok && s < n) {
+    // element header (every lane reads the same bytes: uniform control flow)
+    const uint32_t t = src[s];
+    uint32_t kind = t & 3, len = 0, off = 0, lit = 0;
+    if (kind == 0) {
+      uint32_t x = t >> 2;
+      if (x < 60) {
+        s += 1;
+      } else {
+        const uint32_t nb = x - 59;
+        if (s + 1 + nb > n) { ok = false; break; }
+        x = 0;
+        for (uint32_t i = 0; i < nb; i++) x |= uint32_t(src[s + 1 + i]) << (8 * i);
+        s += 1 + nb;
+      }
+      len = x + 1;  // (x = 2^32 - 1 wraps to 0: corrupt, snappy.Decode's length is 64-bit)
+      if (len == 0 || len > n - s || len > dlen - d) { ok = false; break; }
+      lit = s;
+      s += len;
+    } else if (kind == 1) {
+      if (s + 2 > n) { ok = false; break; }
+      len = 4 + ((t >> 2) & 7);
+      off = ((t & 0xe0) << 3) | src[s + 1];
+      s += 2;
+    } else if (kind == 2) {
+      if (s + 3 > n) { ok = false; break; }
+      len = 1 + (t >> 2);
+      off = uint32_t(src[s + 1]) | uint32_t(src[s + 2]) << 8;
+      s += 3;
+    } else {
+      if (s + 5 > n) { ok = false; break; }
+      len = 1 + (t >> 2);
+      off = uint32_t(src[s + 1]) | uint32_t(src[s + 2]) << 8 | uint32_t(src[s + 3]) << 16 | uint32_t(src[s + 4]) << 24;
+      s += 5;
+    }
+    if (kind != 0 && (off == 0 || off > d || len > dlen - d)) { ok = false; break; }
+    if (kind == 0) {
+      for (uint32_t i = lane; i < len; i += step) dst.set(d + i, src[lit + i]);
+    } else {
+      for (uint32_t i = lane; i < len; i += step) dst.set(d + i, dst.get(d - off + (i % off)));
+    }
+    wave_sync();
+    d += len;
+  }
+  return ok && d == dlen ? d : ~0u;
 }

@@ -1,8 +1,13 @@
 // Host emulation of the device snappy decoder (pebble_amd/csrc/snappy_dec.hip.h):
 // 64 std::threads run the wave's code in lockstep at every wave primitive.
-// Debugging tool only (not part of the product or the tests' checker).
+// Run by tests/test_snappy_emu.py and tests/test_snappy_forms.py; not part of the product.
 //   /opt/rocm/lib/llvm/bin/clang++ -O1 -std=c++20 -pthread scripts/snappy_emu.cpp -o /tmp/snappy_emu
 //   /tmp/snappy_emu in.bin out.bin   (in: a snappy block, uvarint length first)
+//   /tmp/snappy_emu --routes pairs.txt   ("n D" lines: the route each takes)
+// The block goes down the route the kernels give it -- snappy_walk_kernel's
+// lane then sn4_decode, sn_decode, or snappy_wave on one lane -- and the first
+// output line names it: "route walk|lds|global ok 0|1 D <decoded length>".
+// Exit status: 0 decoded, 1 corrupt.
 #include <algorithm>
 #include <barrier>
 #include <cstdint>
@@ -71,38 +76,80 @@ constexpr uint32_t kSnQ = 592;
 }  // namespace phys
 }  // namespace pbl
 
+// physical.hip's uvarint32
+static bool uvarint32(const uint8_t* p, uint64_t n, uint32_t* v, uint32_t* used) {
+  uint64_t x = 0;
+  for (uint32_t i = 0; i < n && i < 10; i++) {
+    x |= uint64_t(p[i] & 0x7f) << (7 * i);
+    if (p[i] < 0x80) {
+      if (x > 0xffffffffull) return false;
+      *v = uint32_t(x);
+      *used = i + 1;
+      return true;
+    }
+  }
+  return false;
+}
+
+// The route snappy2_kernel / snappy4_kernel give a block of n compressed bytes
+// decoding to D, by the compiled conditions.
+static const char* route_of(uint32_t n, uint32_t D) {
+  if (pbl::phys::sn4_walkable(n, D)) return "walk";
+  return n <= pbl::phys::kSnIn && D <= 0xffffu ? "lds" : "global";
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  std::vector<uint8_t> in(1 << 20);  // (zero past the block: the indicator byte's place)
-  const size_t n = fread(in.data(), 1, in.size(), f);
-  fclose(f);
-  uint64_t D = 0;
-  uint32_t used = 0;
-  for (uint32_t i = 0, s = 0; i < 10; i++, s += 7) {
-    D |= uint64_t(in[i] & 0x7f) << s;
-    if (in[i] < 0x80) { used = i + 1; break; }
+  if (argc == 3 && !strcmp(argv[1], "--routes")) {  // a file of "n D" lines: a route per line
+    FILE* f = fopen(argv[2], "r");
+    if (!f) return 2;
+    unsigned long long n, D;
+    while (fscanf(f, "%llu %llu", &n, &D) == 2) puts(route_of(uint32_t(n), uint32_t(D)));
+    fclose(f);
+    return 0;
   }
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 2;
+  std::vector<uint8_t> in(1 << 20);  // (zero past the block: the indicator byte's place)
+  const size_t n = fread(in.data(), 1, in.size() - 64, f);
+  fclose(f);
+  uint32_t D = 0, used = 0;
+  if (!uvarint32(in.data(), n, &D, &used)) {
+    printf("route none ok 0 D 0\n");
+    return 1;
+  }
+  if (D > (64u << 20)) return 3;
+  const char* route = route_of(uint32_t(n), D);
+  // EMU_NO_WALK: a walked block through snappy2's decoder instead
+  if (!strcmp(route, "walk") && getenv("EMU_NO_WALK")) route = n <= pbl::phys::kSnIn ? "lds" : "global";
+  const bool walked = !strcmp(route, "walk"), global = !strcmp(route, "global");
   static pbl::phys::Snap2Lds S;
-  // snappy_walk_kernel's lane for this block, then snappy4's decode (or snappy2's)
-  const bool walked = pbl::phys::sn4_walkable(uint32_t(n), uint32_t(D)) && !getenv("EMU_NO_WALK");
-  if ((!walked && n > pbl::phys::kSnIn) || D > 0xffff) return 3;
-  if (!walked) std::memcpy(S.in, in.data(), n);
-  std::vector<uint8_t> out(D + 64);
-  if (walked) pbl::phys::sn4_walk(in.data(), uint32_t(n), used, uint32_t(D), out.data());
   static pbl::phys::Snap4Lds S4;
-  std::barrier<> bar(64);
-  g_bar = &bar;
-  bool res[64];
-  std::vector<std::thread> th;
-  for (int l = 0; l < 64; l++)
-    th.emplace_back([&, l] {
-      g_lane = l;
-      res[l] = walked ? pbl::phys::sn4_decode(S4, in.data(), uint32_t(n), uint32_t(D), out.data())
-                      : pbl::phys::sn_decode(S, 0, uint32_t(n), used, uint32_t(D), out.data());
-    });
-  for (auto& t : th) t.join();
-  printf("ok %d D %llu\n", int(res[0]), (unsigned long long)D);
+  std::vector<uint8_t> out(size_t(D) + 64);
+  bool res[64] = {false};
+  if (global) {
+    // snappy2_kernel's lane 0 alone: every wave primitive is a no-op
+    std::barrier<> one(1);
+    g_bar = &one;
+    g_lane = 0;
+    res[0] = pbl::phys::snappy_wave(pbl::phys::GlbBytes{in.data()}, uint32_t(n), pbl::phys::GlbBytesW{out.data()}, D, 0,
+                                    1) != ~0u;
+  } else {
+    // snappy_walk_kernel's lane for this block, then snappy4's decode (or snappy2's)
+    if (!walked) std::memcpy(S.in, in.data(), n);
+    if (walked) pbl::phys::sn4_walk(in.data(), uint32_t(n), used, D, out.data());
+    std::barrier<> bar(64);
+    g_bar = &bar;
+    std::vector<std::thread> th;
+    for (int l = 0; l < 64; l++)
+      th.emplace_back([&, l] {
+        g_lane = l;
+        res[l] = walked ? pbl::phys::sn4_decode(S4, in.data(), uint32_t(n), D, out.data())
+                        : pbl::phys::sn_decode(S, 0, uint32_t(n), used, D, out.data());
+      });
+    for (auto& t : th) t.join();
+  }
+  printf("route %s ok %d D %u\n", route, int(res[0]), D);
   if (argc > 2) {
     FILE* g = fopen(argv[2], "wb");
     fwrite(out.data(), 1, D, g);

@@ -16,7 +16,16 @@ blocks.  The h_zstd blocks are 4-stream Huffman literals of at most 1023
 bytes with FSE-coded weights.  Every other form (larger Huffman literals,
 direct weights, treeless and RLE literals, RLE and repeat tables, the 3-byte
 sequence count, the checksum, the header variants, the batch path's
-sequence area running out) is in tests/test_zstd_forms_gpu.py."""
+sequence area running out) is in tests/test_zstd_forms_gpu.py.
+
+The snappy inputs here all come from an encoder (pyarrow's, and the
+reference's hamlet blocks): literals with at most 2 length bytes in canonical
+form, copies with 1- and 2-byte offsets of 4 bytes or more.  The forms an
+encoder never writes (3- and 4-byte literal lengths, non-canonical headers,
+4-byte offsets, 2-byte-offset copies of 1 to 3 bytes), each on all three
+device routes and at output offsets past 32768, the blocks snappy.Decode
+rejects, and output slots other than decompress()'s aligned cap == D ones are
+in tests/test_snappy_forms_gpu.py (tests/snappyutil.py assembles them)."""
 import os
 import random
 

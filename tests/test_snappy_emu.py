@@ -3,7 +3,12 @@ walk, copy-chain resolution by pointer jumping, literal and copy phases) run on
 the host by scripts/snappy_emu.cpp -- 64 threads in lockstep at every wave
 primitive -- against the oracle: hamlet-sst's snappy blocks, config-2-shaped
 blocks and text-like blocks.  CPU-only: it checks the source the GPU build
-compiles before the GPU runs it."""
+compiles before the GPU runs it.
+
+Everything here but one block of 1-byte literals is encoder output.  The
+element forms an encoder never writes, the global-memory route (snappy_wave)
+and the route each block takes are in tests/test_snappy_forms.py, over the
+corpus of tests/snappyutil.py."""
 import os
 import random
 import subprocess
