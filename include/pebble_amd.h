@@ -836,7 +836,7 @@ int pbl_seek_prepare(const pbl_decode_out* decoded, uint32_t n_blocks, uint32_t 
                      void* workspace, uint64_t workspace_bytes, void* stream);
 int pbl_seek_batch(const pbl_decode_out* decoded, uint32_t n_blocks, const pbl_seek_queries* q,
                    pbl_seek_out* out, const void* workspace, uint64_t workspace_bytes, void* stream);
-/* The same search (one function, seek.hip seek_one) over arrays in HOST memory
+/* The same search (one function, seek_core.hip.h seek_one) over arrays in HOST memory
  * (DecodedBatch.to_host(), the oracle's arrays): every pointer of `host`, `q`
  * and `out` is a host pointer; no device call; nothing is read past a key's
  * end.  Table mode builds its fence per call.  Single-threaded. */
@@ -846,6 +846,106 @@ int pbl_seek_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl
  * (whose list is unchanged): sizeof(pbl_seek_queries), its 7 field offsets,
  * sizeof(pbl_seek_out), its 3 field offsets. */
 size_t pbl_seek_struct_layout(uint64_t* out, size_t cap);
+
+/* ---- batched bounded scans over a decoded batch, on the device ----
+ * Query i with bounds [lower_i, upper_i) receives exactly the KVs that a
+ * singleLevelIterator over the batch returns for SetBounds(lower, upper);
+ * First(); Next()... (sstable/reader_iter_single_lvl.go:443-473, :1367-1390,
+ * :1573-1647, skipForward :1765-1840), compacted and copied inside HBM.  The
+ * comparers are those of the seeks above (key_cmp.hip.h) and `decoded` is as
+ * pbl_seek_batch takes it; trailer, val_off, val_bytes and blk_val_base are
+ * needed too, and key_bytes / val_bytes must be readable 16 B past their end.
+ *
+ * Table mode (q->block == NULL): blocks in batch order, from the landing of
+ * SeekGE(lower) to the last KV before the first whose user key is >= upper.  A
+ * block whose status is not PBL_OK is passed over (a PBL_OVERFLOW block, which
+ * keeps a KV range, included).  With hide_obsolete_points the KVs carrying
+ * PBL_KV_OBSOLETE are skipped wherever they lie.  Per-block mode (q->block
+ * given): the same scan confined to block q->block[i]; a block id >= n_blocks
+ * gives an empty result with status PBL_INVALID_ARG, a block that is not
+ * PBL_OK an empty result with that block's status.  An empty lower bound is
+ * First().  "No upper bound" is the per-query flag PBL_SCAN_NO_UPPER (q->flags),
+ * not an empty key; upper <= lower gives an empty result.  The upper bound is
+ * always exclusive: endKeyInclusive belongs to virtual tables and is out of
+ * scope, and so is a per-query limit on the number of KVs.  Queries are
+ * independent: overlapping queries each receive a full copy.
+ *
+ * The result has the layout of a decoded batch with one "block" per query:
+ * out->result is filled so that kv = blk_kv_base[q] + j, offsets at
+ * blk_kv_base[q] + q + j (n_q + 1 of them), key_off / val_off relative to the
+ * query's first byte, blk_status[q], totals (n_bad_blocks = queries whose
+ * status is not PBL_OK).  `restarts` is unused (n_restarts = 0), blk_rst_base
+ * is zeros when given, entry_off and the two tiering arrays are copied when
+ * both sides have them, kv_flags when the result has it.  Everything that
+ * reads a decoded batch reads a scan result: pbl_data_iter_init(result, n, q,
+ * ...), per-block pbl_seek_batch, pbl_scan_batch again.  A query whose key or
+ * value bytes would pass 4 GiB reports PBL_UNSUPPORTED and an empty result (the
+ * offsets are u32).  Optional: range[2q], range[2q + 1] = the source KV index
+ * range [kv_lo, kv_hi) of the query before anything is hidden or passed over
+ * (kv_lo == kv_hi for an empty one); src_kv[k] = the source KV index of result
+ * KV k.
+ *
+ * pbl_scan_prepare (depends on the batch, the comparer and the hide flag only)
+ * builds in the workspace the seek fence of pbl_seek_prepare and the visible
+ * prefix: per aligned tile of 256 source KVs, the exclusive prefix of {visible
+ * KVs, their key bytes, their value bytes} and the tile's first block (28 B per
+ * 256 KVs); visible = block PBL_OK and not (hide and obsolete).  `n_kv` is the
+ * batch's totals.n_kv as the host read it (the workspace is sized by it).
+ * pbl_scan_size then writes blk_*_base, blk_status and totals of out->result
+ * and out->range only (no other array or capacity of out->result is read);
+ * pbl_scan_batch does everything.  When a capacity (kv_cap, key_cap, val_cap)
+ * is exceeded, pbl_scan_batch writes every size and no bytes, and reports
+ * PBL_OVERFLOW in totals.status_mask.  With PBL_SCAN_SIZED in `flags`,
+ * pbl_scan_batch takes the bounds from the workspace as the last pbl_scan_size
+ * with the same queries left them, and runs no search.  All launches are
+ * stream-ordered; no host synchronisation, no global state.  The workspace
+ * (DEVICE, 16-byte aligned, pbl_scan_workspace_bytes(n_queries, n_blocks,
+ * n_kv): nothing in it scales with the ranges' lengths) serves one size / batch
+ * call at a time; the part prepare wrote is only read by them, so any number
+ * of calls with at most n_queries queries, ordered after the prepare, reuse it.
+ * A workspace whose header names another comparer (table mode), n_blocks, hide
+ * flag or a smaller n_kv than the batch holds gives every query an empty
+ * result with status PBL_INVALID_ARG.
+ *
+ * PBL_INVALID_ARG, before any device call: NULL decoded / q / out or a needed
+ * array, comparer > PBL_CMP_CRDB, hide_obsolete_points without kv_flags, only
+ * one of the tiering arrays, a workspace that is NULL, not 16-byte aligned or
+ * shorter than pbl_scan_workspace_bytes(q->n, n_blocks, n_kv), unknown flags.
+ */
+#define PBL_SCAN_NO_UPPER 0x1u  /* pbl_scan_queries.flags[i]: no upper bound (upper key i is ignored) */
+#define PBL_SCAN_SIZED    0x1u  /* pbl_scan_batch flags: bounds are in the workspace (see above) */
+
+typedef struct pbl_scan_queries {
+  const uint8_t*  lower_bytes; /* DEVICE; readable 16 B past the last key */
+  const uint64_t* lower_off;   /* DEVICE [n + 1] */
+  const uint8_t*  upper_bytes; /* DEVICE; readable 16 B past the last key */
+  const uint64_t* upper_off;   /* DEVICE [n + 1] */
+  const uint8_t*  flags;       /* DEVICE [n] PBL_SCAN_* per query, or NULL (all 0) */
+  const uint32_t* block;       /* DEVICE [n], or NULL (see modes) */
+  uint32_t n, comparer /* PBL_CMP_* */, hide_obsolete_points, reserved;
+} pbl_scan_queries;
+
+typedef struct pbl_scan_out {
+  pbl_decode_out result;  /* one "block" per query (see above); workspace fields unused */
+  uint64_t* range;        /* DEVICE [2n], optional */
+  uint64_t* src_kv;       /* DEVICE [result.kv_cap], optional */
+} pbl_scan_out;
+
+uint64_t pbl_scan_workspace_bytes(uint32_t n_queries, uint32_t n_blocks, uint64_t n_kv);
+int pbl_scan_prepare(const pbl_decode_out* decoded, uint32_t n_blocks, uint64_t n_kv, uint32_t comparer,
+                     uint32_t hide_obsolete_points, void* workspace, uint64_t workspace_bytes, void* stream);
+int pbl_scan_size(const pbl_decode_out* decoded, uint32_t n_blocks, uint64_t n_kv, const pbl_scan_queries* q,
+                  pbl_scan_out* out, void* workspace, uint64_t workspace_bytes, void* stream);
+int pbl_scan_batch(const pbl_decode_out* decoded, uint32_t n_blocks, uint64_t n_kv, const pbl_scan_queries* q,
+                   pbl_scan_out* out, void* workspace, uint64_t workspace_bytes, uint32_t flags, void* stream);
+/* The same bounds search (one function, scan.hip bounds_one over seek_core.hip.h)
+ * over arrays in HOST memory, followed by a plain gather: every pointer is a
+ * host pointer, no device call, no workspace, nothing read past a key's end.
+ * Sizes, statuses, overflow rule and outputs as pbl_scan_batch.  Single-threaded. */
+int pbl_scan_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl_scan_queries* q, pbl_scan_out* out);
+/* sizeof(pbl_scan_queries), its 10 field offsets, sizeof(pbl_scan_out), its 3
+ * field offsets (pbl_struct_layout's and pbl_seek_struct_layout's lists are unchanged). */
+size_t pbl_scan_struct_layout(uint64_t* out, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,21 @@ class SeekOutC(ctypes.Structure):  # pbl_seek_out
     _fields_ = [("kv", _vp), ("block", _vp), ("flags", _vp)]
 
 
+# batched bounded scans (pbl_scan_batch)
+PBL_SCAN_NO_UPPER = 0x1  # pbl_scan_queries.flags[i]
+PBL_SCAN_SIZED = 0x1     # pbl_scan_batch flags
+
+
+class ScanQueriesC(ctypes.Structure):  # pbl_scan_queries
+    _fields_ = [("lower_bytes", _vp), ("lower_off", _vp), ("upper_bytes", _vp), ("upper_off", _vp),
+                ("flags", _vp), ("block", _vp), ("n", ctypes.c_uint32), ("comparer", ctypes.c_uint32),
+                ("hide_obsolete_points", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ScanOutC(ctypes.Structure):  # pbl_scan_out
+    _fields_ = [("result", DecodeOutC), ("range", _vp), ("src_kv", _vp)]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -230,6 +245,18 @@ SIGNATURES = {
     "pbl_seek_batch_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
                                            ctypes.POINTER(SeekQueriesC), ctypes.POINTER(SeekOutC)]),
     "pbl_seek_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_scan_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+    "pbl_scan_prepare": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                        ctypes.c_uint32, _vp, ctypes.c_uint64, _vp]),
+    "pbl_scan_size": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32, ctypes.c_uint64,
+                                     ctypes.POINTER(ScanQueriesC), ctypes.POINTER(ScanOutC), _vp, ctypes.c_uint64,
+                                     _vp]),
+    "pbl_scan_batch": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32, ctypes.c_uint64,
+                                      ctypes.POINTER(ScanQueriesC), ctypes.POINTER(ScanOutC), _vp, ctypes.c_uint64,
+                                      ctypes.c_uint32, _vp]),
+    "pbl_scan_batch_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
+                                           ctypes.POINTER(ScanQueriesC), ctypes.POINTER(ScanOutC)]),
+    "pbl_scan_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

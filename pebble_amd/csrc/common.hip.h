@@ -495,6 +495,46 @@ __device__ inline void store16(uint8_t* base_, uint64_t ga, uint64_t lo, uint64_
   }
 }
 
+// dst[0, n) = src[0, n) by 16-B chunks (unaligned global loads / stores; the
+// sources are readable 15 bytes past their end), exact at the tail.
+typedef u32x4 u32x4_u __attribute__((aligned(1)));
+typedef uint64_t u64_u __attribute__((aligned(1)));
+typedef uint32_t u32_u __attribute__((aligned(1)));
+typedef uint16_t u16_u __attribute__((aligned(1)));
+__device__ __forceinline__ void copy_chunks(gptr<uint8_t> dst, gptr<const uint8_t> src, uint32_t n) {
+  uint32_t c = 0;
+  for (; c + 64 <= n; c += 64) {
+    u32x4 x[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) x[u] = *(gptr<const u32x4_u>)(src + c + 16 * u);
+#pragma unroll
+    for (int u = 0; u < 4; u++) *(gptr<u32x4_u>)(dst + c + 16 * u) = x[u];
+  }
+  for (; c + 16 <= n; c += 16) *(gptr<u32x4_u>)(dst + c) = *(gptr<const u32x4_u>)(src + c);
+  if (c < n) {
+    const u32x4 w = *(gptr<const u32x4_u>)(src + c);
+    const uint32_t r = n - c;
+    uint64_t lo = uint64_t(w.x) | uint64_t(w.y) << 32, hi = uint64_t(w.z) | uint64_t(w.w) << 32;
+    uint32_t o = c;
+    if (r & 8) {
+      *(gptr<u64_u>)(dst + o) = lo;
+      lo = hi;
+      o += 8;
+    }
+    if (r & 4) {
+      *(gptr<u32_u>)(dst + o) = uint32_t(lo);
+      lo >>= 32;
+      o += 4;
+    }
+    if (r & 2) {
+      *(gptr<u16_u>)(dst + o) = uint16_t(lo);
+      lo >>= 16;
+      o += 2;
+    }
+    if (r & 1) dst[o] = uint8_t(lo);
+  }
+}
+
 // Per-block results and batch totals, written by lane 0 of wave 0.
 __device__ inline void write_block_meta(const pbl_decode_out& O, uint32_t b, uint32_t nb, uint32_t status,
                                         const uint64_t excl[kNumComp], const uint64_t agg[kNumComp],

@@ -243,6 +243,7 @@ class Table:
         self._meta_raw = None
         self._props = None
         self._seek = None
+        self._scan = {}
 
     # -- the physical step for any set of handles already on the device ----------
     def _blocks(self, off: torch.Tensor, length: torch.Tensor, fmt: int, flags: int = 0) -> BlockBatch:
@@ -448,3 +449,28 @@ class Table:
         (PBL_SEEK_EXACT), else -1: int64 [n]."""
         r = self.seek_ge(keys)
         return torch.where((r.flags & N.PBL_SEEK_EXACT) != 0, r.kv, torch.full_like(r.kv, -1))
+
+    # -- range scans over the decoded table (pebble_amd.scan) ----------------------
+    def _scannable(self, resolve: bool, hide: bool, n: int):
+        """The table decoded once per `resolve`, with one ScanIndex per hide flag."""
+        from .scan import prepare
+        if resolve not in self._scan:
+            d = self._seekable()[0] if not resolve else self.decode(resolve=True)
+            if d.read_totals().status_mask:
+                raise DecodeError("corrupt data block")
+            self._scan[resolve] = (d, {})
+        d, idx = self._scan[resolve]
+        if hide not in idx or idx[hide].n_queries < n:
+            idx[hide] = prepare(d, self.comparer(), hide, max(n, 1024))
+        return d, idx[hide]
+
+    def scan(self, lowers, uppers, hide_obsolete_points: bool = False, resolve: bool = True):
+        """Per range [lower, upper) (None = unbounded), the KVs that
+        singleLevelIterator returns for SetBounds(lower, upper); First();
+        Next()...: a ScanResult whose batch has one "block" per range and the
+        values `decode(resolve=resolve)` holds; `range` and `src_kv` index that
+        decode's KVs."""
+        from .scan import scan
+        d, idx = self._scannable(bool(resolve), bool(hide_obsolete_points), len(lowers))
+        return scan(d, lowers, uppers, comparer=idx.comparer, hide_obsolete_points=bool(hide_obsolete_points),
+                    index=idx)
