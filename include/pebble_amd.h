@@ -947,6 +947,98 @@ int pbl_scan_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl
  * field offsets (pbl_struct_layout's and pbl_seek_struct_layout's lists are unchanged). */
 size_t pbl_scan_struct_layout(uint64_t* out, size_t cap);
 
+/* ---- batched k-way merge of sorted decoded batches, on the device ----
+ * n_runs decoded batches ("runs", 1 <= n_runs <= PBL_MERGE_MAX_RUNS), all with
+ * the same n_blocks, go in; one decoded batch comes out.  Result block q is the
+ * merge of block q of every run: exactly the sequence mergingIter.First();
+ * Next()... yields over those inputs.  The usual runs are scan results of
+ * several tables for the same ranges (one "block" per range), and every run is
+ * as pbl_scan_batch takes a batch (key_bytes / val_bytes readable 16 B past
+ * their end).
+ *
+ * Order: mergingIterHeap.less / base.InternalCompare (merging_iter_heap.go:55-67,
+ * internal/base/internal.go:431-437): user key ascending under the comparer
+ * (PBL_CMP_DEFAULT / TESTKEYS / CRDB, key_cmp.hip.h), then trailer DESCENDING.
+ * Ties: two KVs that compare equal in both go in run order, the lower run index
+ * first; within a run they keep the run's order.  (The reference leaves that
+ * case to the shape of its heap, and it does not arise between the levels of
+ * one LSM, whose sequence numbers are distinct.)
+ *
+ * Out of scope: nothing is dropped or collapsed.  Shadowed versions,
+ * tombstones, snapshots, MERGE operands, range deletions and compact.Iter are
+ * the consumer's; hiding obsolete points is the scan's job (pbl_scan_batch)
+ * and is not repeated here.
+ *
+ * The result has the layout of a decoded batch with one block per q, as a scan
+ * result: kv = blk_kv_base[q] + j, offsets at blk_kv_base[q] + q + j (n_q + 1
+ * of them), key_off / val_off relative to the block's first byte,
+ * blk_status[q], totals (n_bad_blocks = result blocks whose status is not
+ * PBL_OK).  `restarts` is unused (n_restarts = 0), blk_rst_base is zeros when
+ * given.  kv_flags, entry_off and the two tiering arrays are copied when the
+ * result has them; a run without one of them gives zeros there.  Optional:
+ * src_run[k] = the run result KV k came from, src_kv[k] = its KV index in
+ * that run.  Everything that reads a decoded batch reads a merge result,
+ * pbl_merge_batch included.
+ *
+ * A result block is empty, and its neighbours are unaffected, when
+ *  - a run's block q is not PBL_OK: the result block gets the first non-OK
+ *    status among block q of the runs, in run order;
+ *  - the summed KV count reaches 2^32, or the summed key or value bytes pass
+ *    4 GiB (the offsets are u32): PBL_UNSUPPORTED;
+ *  - a run's block q is not sorted under (comparer, trailer descending),
+ *    non-strictly, so that a merge result can be merged again:
+ *    PBL_INVALID_ARG.  An unsorted input never leads to a read or write
+ *    outside the arrays.
+ *
+ * pbl_merge_size writes blk_*_base, blk_status and totals of out->result only
+ * (no other array or capacity of out->result is read); pbl_merge_batch does
+ * everything.  When a capacity (kv_cap, key_cap, val_cap) is exceeded,
+ * pbl_merge_batch writes every size and no bytes, and reports PBL_OVERFLOW in
+ * totals.status_mask.  With PBL_MERGE_SIZED in `flags`, pbl_merge_batch takes
+ * the statuses and sizes from the workspace as the last pbl_merge_size over the
+ * same runs left them and does not validate again.  All launches are
+ * stream-ordered; no host synchronisation, no global state.  The workspace
+ * (DEVICE, 16-byte aligned, pbl_merge_workspace_bytes(n_runs, n_blocks,
+ * n_kv_total), known before any data is read) serves one call at a time;
+ * n_kv_total is the sum of the runs' totals.n_kv as the host read them.  Runs
+ * that hold more KVs than that give every block PBL_INVALID_ARG.
+ *
+ * PBL_INVALID_ARG, before any device call: NULL runs / out or a needed array,
+ * n_runs of 0 or more than PBL_MERGE_MAX_RUNS, comparer > PBL_CMP_CRDB, only
+ * one of the tiering arrays (in a run or in the result), a workspace that is
+ * NULL, not 16-byte aligned or too short, unknown flags.
+ */
+#define PBL_MERGE_MAX_RUNS 16
+#define PBL_MERGE_SIZED 0x1u  /* pbl_merge_batch flags: statuses and sizes are in the workspace (see above) */
+
+typedef struct pbl_merge_runs {
+  const pbl_decode_out* runs; /* HOST array [n_runs]; the arrays each names are DEVICE (HOST for
+                                 pbl_merge_batch_host); capacities and workspace fields unused */
+  uint32_t n_runs, n_blocks, comparer /* PBL_CMP_* */, reserved;
+  uint64_t n_kv_total;        /* see above; unused by pbl_merge_batch_host */
+} pbl_merge_runs;
+
+typedef struct pbl_merge_out {
+  pbl_decode_out result;  /* one block per q (see above); workspace fields unused */
+  uint8_t* src_run;       /* [result.kv_cap], optional */
+  uint64_t* src_kv;       /* [result.kv_cap], optional */
+} pbl_merge_out;
+
+uint64_t pbl_merge_workspace_bytes(uint32_t n_runs, uint32_t n_blocks, uint64_t n_kv_total);
+int pbl_merge_size(const pbl_merge_runs* runs, pbl_merge_out* out, void* workspace, uint64_t workspace_bytes,
+                   void* stream);
+int pbl_merge_batch(const pbl_merge_runs* runs, pbl_merge_out* out, void* workspace, uint64_t workspace_bytes,
+                    uint32_t flags, void* stream);
+/* The same order (one function, key_cmp.hip.h ikey_cmp) over arrays in HOST
+ * memory by a different algorithm: a plain k-way merge that repeatedly takes
+ * the least head, the lowest run among equals, so that the two check each
+ * other.  No device call, no workspace, nothing read past a key's end.  Sizes,
+ * statuses, overflow rule and outputs as pbl_merge_batch.  Single-threaded. */
+int pbl_merge_batch_host(const pbl_merge_runs* runs, pbl_merge_out* out);
+/* sizeof(pbl_merge_runs), its 6 field offsets, sizeof(pbl_merge_out), its 3
+ * field offsets (the other layout lists are unchanged). */
+size_t pbl_merge_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ C-ABI declared in include/pebble_amd.h.  This package is the host layer:
   pebble_amd.rowblk  Writer, NewIter/Iter mirroring sstable/rowblk
   pebble_amd.shard   multi-GPU sharding + RCCL offset concat
   pebble_amd.seek    batched SeekGE / SeekLT over a DecodedBatch, on the device
+  pebble_amd.scan    batched bounded scans over a DecodedBatch, on the device
+  pebble_amd.merge   batched k-way merge of sorted DecodedBatches, on the device
 """
 from . import _native  # noqa: F401
 

@@ -210,6 +210,20 @@ class ScanOutC(ctypes.Structure):  # pbl_scan_out
     _fields_ = [("result", DecodeOutC), ("range", _vp), ("src_kv", _vp)]
 
 
+# batched k-way merge (pbl_merge_batch)
+PBL_MERGE_MAX_RUNS = 16
+PBL_MERGE_SIZED = 0x1  # pbl_merge_batch flags
+
+
+class MergeRunsC(ctypes.Structure):  # pbl_merge_runs
+    _fields_ = [("runs", ctypes.POINTER(DecodeOutC)), ("n_runs", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32),
+                ("comparer", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_kv_total", ctypes.c_uint64)]
+
+
+class MergeOutC(ctypes.Structure):  # pbl_merge_out
+    _fields_ = [("result", DecodeOutC), ("src_run", _vp), ("src_kv", _vp)]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -257,6 +271,13 @@ SIGNATURES = {
     "pbl_scan_batch_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
                                            ctypes.POINTER(ScanQueriesC), ctypes.POINTER(ScanOutC)]),
     "pbl_scan_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_merge_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+    "pbl_merge_size": (ctypes.c_int, [ctypes.POINTER(MergeRunsC), ctypes.POINTER(MergeOutC), _vp, ctypes.c_uint64,
+                                      _vp]),
+    "pbl_merge_batch": (ctypes.c_int, [ctypes.POINTER(MergeRunsC), ctypes.POINTER(MergeOutC), _vp, ctypes.c_uint64,
+                                       ctypes.c_uint32, _vp]),
+    "pbl_merge_batch_host": (ctypes.c_int, [ctypes.POINTER(MergeRunsC), ctypes.POINTER(MergeOutC)]),
+    "pbl_merge_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

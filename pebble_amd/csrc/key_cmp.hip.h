@@ -133,6 +133,15 @@ PBL_HD inline int key_cmp(uint32_t cmp, kptr<R> a, uint64_t al, kptr<R> b, uint6
     default: return R::bytes_cmp(a, al, b, bl);
   }
 }
+// base.InternalCompare (internal/base/internal.go:431-437), which is also
+// mergingIterHeap.less (merging_iter_heap.go:55-67): the user keys under the
+// comparer, then the trailers in reverse (the newer version sorts first).
+template <class R, uint32_t kCmp>
+PBL_HD inline int ikey_cmp(kptr<R> a, uint64_t al, uint64_t atr, kptr<R> b, uint64_t bl, uint64_t btr) {
+  const int c = key_cmp<R>(kCmp, a, al, b, bl);
+  if (c) return c;
+  return atr > btr ? -1 : atr < btr ? 1 : 0;
+}
 template <class R>
 PBL_HD inline uint64_t key_split(uint32_t cmp, kptr<R> a, uint64_t n) {
   switch (cmp) {

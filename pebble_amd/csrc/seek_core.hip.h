@@ -139,6 +139,36 @@ PBL_HD inline uint32_t lower(uint32_t cmp, const Block<R>& B, cmp::kptr<R> k, ui
   return lo;
 }
 
+// The same search over internal keys (cmp::ikey_cmp; `tr`: the trailers of the
+// block's KVs): the first KV of the block that is >= the internal key (k, ktr),
+// or with kAfter the first that is > it (n when there is none).  The block is
+// sorted under ikey_cmp, non-strictly (merge.hip checks that before it
+// searches).
+template <class R, uint32_t kCmp, bool kAfter>
+PBL_HD inline uint32_t ibound(const Block<R>& B, typename R::template ptr<const uint64_t> tr, cmp::kptr<R> k,
+                              uint64_t kl, uint64_t ktr) {
+  uint32_t lo = 0, hi = B.n;
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    uint64_t ml;
+    const cmp::kptr<R> mk = B.key(m, &ml);
+    const int c = cmp::ikey_cmp<R, kCmp>(mk, ml, tr[m], k, kl, ktr);
+    if (kAfter ? c <= 0 : c < 0) lo = m + 1;
+    else hi = m;
+  }
+  return lo;
+}
+template <class R, uint32_t kCmp>
+PBL_HD inline uint32_t ilower(const Block<R>& B, typename R::template ptr<const uint64_t> tr, cmp::kptr<R> k,
+                              uint64_t kl, uint64_t ktr) {
+  return ibound<R, kCmp, false>(B, tr, k, kl, ktr);
+}
+template <class R, uint32_t kCmp>
+PBL_HD inline uint32_t iupper(const Block<R>& B, typename R::template ptr<const uint64_t> tr, cmp::kptr<R> k,
+                              uint64_t kl, uint64_t ktr) {
+  return ibound<R, kCmp, true>(B, tr, k, kl, ktr);
+}
+
 // The fence record of block b (a PBL_OK block holding at least one KV).
 template <class R>
 PBL_HD inline Fence fence_of(uint32_t cmp, const View<R>& V, uint32_t b) {
