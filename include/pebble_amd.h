@@ -1039,6 +1039,114 @@ int pbl_merge_batch_host(const pbl_merge_runs* runs, pbl_merge_out* out);
  * field offsets (the other layout lists are unchanged). */
 size_t pbl_merge_struct_layout(uint64_t* out, size_t cap);
 
+/* ---- batched snapshot-visible view of a sorted decoded batch, on the device ----
+ * One decoded batch goes in, one comes out with the same n_blocks.  Every input
+ * block is sorted under (comparer, trailer descending), as a merge result, a
+ * scan result or a decode of one table's blocks is.  Result block q is what
+ * Iterator.First(); Next()... returns over block q's KVs as the point-key
+ * stream, with DefaultMerger: the step pebble.Iterator.findNextEntry /
+ * mergeNext takes on top of mergingIter.  Blocks are independent: a user key
+ * that ends block q and starts block q + 1 gives two groups.
+ *
+ * Per block:
+ *  1. Visibility (base.Visible, internal/base/internal.go:524; the filter sits
+ *     in mergingIter, merging_iter.go:766): a KV is visible iff
+ *     trailer >> 8 < snapshot.  A snapshot of PBL_SEQNUM_MAX (or more) sees
+ *     everything, sequence number PBL_SEQNUM_MAX included.  The batch bit
+ *     (base.SeqNumBatchBit) is NOT interpreted: an indexed batch's keys are
+ *     not special here.  Invisible KVs are skipped everywhere, inside a MERGE
+ *     chain too.
+ *  2. A group is a maximal sequence of KVs whose user keys compare equal under
+ *     the comparer (the reference's i.equal).  Under TESTKEYS and CRDB keys
+ *     with different bytes can be equal; a result carries the bytes of the KV
+ *     that produced it.
+ *  3. The head is the group's first visible KV (iterator.go:649-664):
+ *     DEL / SINGLEDEL / DELSIZED: the group yields nothing.
+ *     SET / SETWITHDEL: one result KV.  Key, trailer, value, tiering meta,
+ *     entry_off and the value-kind flag bits (PBL_KV_VALBLK_HANDLE /
+ *     PBL_KV_BLOB_HANDLE) are the head's; the other flag bits are zero.
+ *     MERGE (iterator.go:1239-1305): the following visible KVs of the group are
+ *     gone through.  A MERGE is an operand and continues the chain; a SET /
+ *     SETWITHDEL is an operand and ends it; a deletion kind ends it without
+ *     being an operand; so does the group's end.  One result KV: key, trailer
+ *     and the rest are the head's, the value is the operands' values
+ *     concatenated OLDEST FIRST (AppendValueMerger with MergeOlder prepending,
+ *     internal/base/merger.go).
+ *  4. With PBL_VISIBLE_KEEP_OPERANDS every operand of a chain is a result KV of
+ *     its own, in source order (newest first), unconcatenated, for a caller
+ *     with its own merger.  Groups headed by a SET are as above.
+ *  5. Statuses.  A result block is empty, its neighbours unaffected, when
+ *      - the input block is not PBL_OK: that status;
+ *      - the block is not sorted under (comparer, trailer descending),
+ *        non-strictly: PBL_INVALID_ARG, as pbl_merge_batch;
+ *      - a KV has PBL_KV_INVALID_KEY, or a kind other than the six above
+ *        (visible or not; range keys and range deletions are out of scope, the
+ *        rest is corruption to the reference): PBL_UNSUPPORTED;
+ *      - without KEEP_OPERANDS, a chain of more than one operand holds a value
+ *        that is a handle: PBL_UNSUPPORTED;
+ *      - the block's result KVs reach 2^32, or its key or value bytes pass
+ *        4 GiB: PBL_UNSUPPORTED.
+ *     Where several apply, the first in this list is reported.
+ *     PBL_KV_OBSOLETE is ignored: an obsolete point is shadowed by definition.
+ *  6. Optional, per result KV: src_kv = the index in the input of the head (of
+ *     the operand under KEEP_OPERANDS); n_src = the number of source KVs whose
+ *     bytes the result value holds (under KEEP_OPERANDS: the chain's length at
+ *     the chain's first KV, 0 at the others).
+ *
+ * The result has the layout of a decoded batch with one block per q, as a scan
+ * or merge result (restarts unused, blk_rst_base zeros when given); everything
+ * that reads a decoded batch reads it.  The input is as pbl_scan_batch takes a
+ * batch (key_bytes / val_bytes readable 16 B past their end).
+ *
+ * Sizing and overflow as pbl_merge_*: pbl_visible_size writes blk_*_base,
+ * blk_status and totals only; pbl_visible_batch does everything, and on a
+ * capacity overflow writes every size, no bytes, and PBL_OVERFLOW in
+ * totals.status_mask.  With PBL_VISIBLE_SIZED, pbl_visible_batch takes
+ * statuses, sizes and roles from the workspace as the last pbl_visible_size
+ * over the same input, snapshot and KEEP_OPERANDS left them.  The workspace
+ * (DEVICE, 16-byte aligned, pbl_visible_workspace_bytes(n_blocks, n_kv)) serves
+ * one call at a time; nothing in it scales with a group's length.  n_kv is the
+ * batch's totals.n_kv as the host read it; a batch that holds more gives every
+ * block PBL_INVALID_ARG.  All launches are stream-ordered.
+ *
+ * PBL_INVALID_ARG, before any device call: NULL in / out or a needed array,
+ * comparer > PBL_CMP_CRDB, only one of the tiering arrays (in the input or in
+ * the result), a workspace that is NULL, not 16-byte aligned or too short,
+ * unknown flags (PBL_VISIBLE_SIZED is unknown to pbl_visible_size and to
+ * pbl_visible_batch_host).
+ */
+#define PBL_SEQNUM_MAX ((1ull << 56) - 1)   /* base.SeqNumMax */
+#define PBL_VISIBLE_SIZED 0x1u          /* pbl_visible_batch: statuses, sizes and roles are in the workspace */
+#define PBL_VISIBLE_KEEP_OPERANDS 0x2u  /* rule 4 */
+
+typedef struct pbl_visible_in {
+  pbl_decode_out batch;  /* the arrays are DEVICE (HOST for pbl_visible_batch_host); capacities and workspace fields unused */
+  uint32_t n_blocks, comparer /* PBL_CMP_* */;
+  uint64_t n_kv;         /* see above; unused by pbl_visible_batch_host */
+  uint64_t snapshot;
+} pbl_visible_in;
+
+typedef struct pbl_visible_out {
+  pbl_decode_out result;  /* one block per q (see above); workspace fields unused */
+  uint64_t* src_kv;       /* [result.kv_cap], optional */
+  uint32_t* n_src;        /* [result.kv_cap], optional */
+} pbl_visible_out;
+
+uint64_t pbl_visible_workspace_bytes(uint32_t n_blocks, uint64_t n_kv);
+int pbl_visible_size(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
+                     uint32_t flags, void* stream);
+int pbl_visible_batch(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
+                      uint32_t flags, void* stream);
+/* The same rules over arrays in HOST memory as the plain sequential state
+ * machine (a different algorithm from the device's scan, so that the two check
+ * each other).  No device call, no workspace, nothing read past a key's end.
+ * Sizes, statuses, overflow rule and outputs as pbl_visible_batch.
+ * Single-threaded. */
+int pbl_visible_batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint32_t flags);
+/* sizeof(pbl_visible_in), its 5 field offsets, sizeof(pbl_visible_out), its 3
+ * field offsets (the other layout lists are unchanged). */
+size_t pbl_visible_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

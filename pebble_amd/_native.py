@@ -224,6 +224,21 @@ class MergeOutC(ctypes.Structure):  # pbl_merge_out
     _fields_ = [("result", DecodeOutC), ("src_run", _vp), ("src_kv", _vp)]
 
 
+# batched snapshot-visible view (pbl_visible_batch)
+PBL_SEQNUM_MAX = (1 << 56) - 1
+PBL_VISIBLE_SIZED = 0x1           # pbl_visible_batch flags
+PBL_VISIBLE_KEEP_OPERANDS = 0x2   # pbl_visible_size / pbl_visible_batch / pbl_visible_batch_host flags
+
+
+class VisibleInC(ctypes.Structure):  # pbl_visible_in
+    _fields_ = [("batch", DecodeOutC), ("n_blocks", ctypes.c_uint32), ("comparer", ctypes.c_uint32),
+                ("n_kv", ctypes.c_uint64), ("snapshot", ctypes.c_uint64)]
+
+
+class VisibleOutC(ctypes.Structure):  # pbl_visible_out
+    _fields_ = [("result", DecodeOutC), ("src_kv", _vp), ("n_src", _vp)]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -278,6 +293,14 @@ SIGNATURES = {
                                        ctypes.c_uint32, _vp]),
     "pbl_merge_batch_host": (ctypes.c_int, [ctypes.POINTER(MergeRunsC), ctypes.POINTER(MergeOutC)]),
     "pbl_merge_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_visible_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint64]),
+    "pbl_visible_size": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC), _vp, ctypes.c_uint64,
+                                        ctypes.c_uint32, _vp]),
+    "pbl_visible_batch": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC), _vp, ctypes.c_uint64,
+                                         ctypes.c_uint32, _vp]),
+    "pbl_visible_batch_host": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC),
+                                              ctypes.c_uint32]),
+    "pbl_visible_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
