@@ -26,6 +26,15 @@ constexpr int kNumComp = 4; // look-back components: n_kv, key bytes, value byte
 // 2 / 3 / 4 GiB/s) 8 windows 972 / 1199 / 857, 4: 999 / - / -, 2: 1036 / 1270
 // / 893, 1: 1035 / 1228 / -.
 constexpr int kLbWin = PBL_LB_WIN;
+#ifndef PBL_LB_L2
+#define PBL_LB_L2 0  // compiled out: the measurements are in DESIGN.md 3.1 (round 9)
+#endif
+// Two-level look-back (the row pool kernel and the blocks it hands to
+// block_big / block_slow; every other kernel keeps the one-level form): a
+// resolve also loads one window of chunk records and adds whole chunks of 64
+// where they are there, instead of a round trip per 128 records.  0: the
+// one-level form everywhere.
+constexpr bool kLbL2 = PBL_LB_L2 != 0;
 
 // ---- workspace layout ------------------------------------------------------
 // [0,256): ticket counter (u32 [0]), big-block count (u32 [1], row pipeline), pad.  Then
@@ -38,6 +47,14 @@ constexpr int kLbWin = PBL_LB_WIN;
 //                               w0 = PfxWide (inclusive prefix too wide: in pfx[])
 //   pfx[kNumComp][n_blocks]   wide inclusive prefixes {state | value}
 //   wide[kNumComp][n_blocks]  wide aggregates {state | value}
+//   l2[ceil(n_blocks / 64)]   one 16-B record per chunk of 64 block ids (level 2
+//                             of the look-back, PBL_LB_L2), both halves tagged
+//                             alike and packed as a prefix is:
+//                               Agg: the chunk's four summed counts, or
+//                               Pfx: the chunk's inclusive prefix
+//                             written only by the wave that resolves the chunk's
+//                             last block, and never waited for: a resolve that
+//                             finds one absent walks the chunk's records instead
 // All written and read with agent-scope relaxed 8-byte atomics (sc1): each word
 // carries its own state, so a reader that sees a record before the words it
 // announces simply polls those (no fences; MI355X_MICROARCH.md "Valid forms",
@@ -72,15 +89,19 @@ constexpr int kPkShift[kNumComp] = {0, 14, 32, 50};
 // packed inclusive prefix: w0 = n_kv 31 | key 30, w1 = val 37 | rst 24
 constexpr int kPfBits[kNumComp] = {31, 30, 37, 24};
 
-__host__ __device__ inline uint64_t ws_bytes(uint32_t n_blocks) {
+constexpr uint32_t kL2Chunk = 64;  // block ids per chunk record (l2[])
+__host__ __device__ inline uint64_t ws_l2_offset(uint32_t n_blocks) {
   return kWsHeader + uint64_t(2 + 2 * kNumComp) * n_blocks * 8ull;
+}
+__host__ __device__ inline uint64_t ws_bytes(uint32_t n_blocks) {
+  return ws_l2_offset(n_blocks) + 16ull * ((uint64_t(n_blocks) + kL2Chunk - 1) / kL2Chunk);
 }
 // Two-pass forms (a size pass, the bases scan, then the outputs): per-block
 // restart counts, scanned in place into restart bases ([n_blocks] = total).
-// The last n_blocks + 1 words of the look-back area, which the scan's own
-// per-tile look-back (n_blocks / 1024 records) never reaches.
+// The last n_blocks + 1 words of the per-block look-back arrays, which the
+// scan's own per-tile look-back (n_blocks / 1024 records) never reaches.
 __host__ __device__ inline uint64_t ws_rcnt_offset(uint32_t n_blocks) {
-  return ws_bytes(n_blocks) - 8ull * (n_blocks + 1);
+  return ws_l2_offset(n_blocks) - 8ull * (n_blocks + 1);
 }
 #ifdef PBL_STAMPS
 constexpr uint64_t kStampWords = 16;  // diagnostic build: per-block phase stamps
@@ -259,9 +280,29 @@ struct LbPtrs {
   uint64_t* rec;   // [2 * n_blocks]
   uint64_t* pfx;   // [kNumComp * n_blocks]
   uint64_t* wide;  // [kNumComp * n_blocks]
+  uint64_t* l2;    // [2 * ceil(n_blocks / 64)]
   __device__ LbPtrs(uint64_t* st, uint32_t n_blocks)
-      : rec(st), pfx(st + 2ull * n_blocks), wide(st + 2ull * n_blocks + uint64_t(kNumComp) * n_blocks) {}
+      : rec(st), pfx(st + 2ull * n_blocks), wide(st + 2ull * n_blocks + uint64_t(kNumComp) * n_blocks),
+        l2(st + (ws_l2_offset(n_blocks) - kWsHeader) / 8) {}
 };
+
+// A chunk record's two words (Agg or Pfx: the same packing as a packed prefix).
+__device__ inline void l2_store(const LbPtrs& P, uint32_t chunk, uint64_t tag, const uint64_t p[kNumComp]) {
+  st_agent(P.l2 + 2ull * chunk + 1, tag | p[2] | (p[3] << kPfBits[2]));
+  st_agent(P.l2 + 2ull * chunk, tag | p[0] | (p[1] << kPfBits[0]));
+}
+
+#ifdef PBL_STAMPS
+// diagnostic build: what one resolve cost (scripts/pool_stamps.py)
+struct LbDiag {
+  uint32_t trips, recs, recs2;  // round trips; level-1 and level-2 records consumed
+  uint64_t poll;                // cycles in the single-lane poll on an unpublished predecessor
+};
+#define LBDIAG(...) __VA_ARGS__
+#else
+struct LbDiag {};
+#define LBDIAG(...)
+#endif
 
 // Store block v's inclusive prefix `p` (lanes 0-3 of the calling wave).
 __device__ inline void lb_store_pfx(const LbPtrs& P, uint32_t n_blocks, uint32_t v, const uint64_t p[kNumComp]) {
@@ -329,18 +370,40 @@ __device__ inline void lb_fetch4(uint64_t* src, uint32_t n_blocks, int64_t idx, 
 
 // Windows of predecessor records loaded in one round trip: lane l of window k
 // holds rec[top - 64k - l] (w0 and w1).
-template <int W>
-struct LbWindows {
+// L2 (two-level form): the windows stop at the start of the chunk before
+// (top + 1)'s, 64..127 records (a lane past that edge holds an empty
+// aggregate), and lane l of one more window holds the record of chunk
+// chunk(top + 1) - 2 - l.
+template <bool L2>
+struct LbChunkWin {};
+template <>
+struct LbChunkWin<true> {
+  uint64_t c0, c1;
+};
+template <int W, bool L2 = false>
+struct LbWindows : LbChunkWin<L2> {
+  static_assert(!L2 || W >= 2, "two windows reach the chunk edge");
   uint64_t w0[W], w1[W];
   int64_t top;
+  // the chunk of block top + 1
+  __device__ inline int64_t chunk() const { return (top + 1) >> 6; }
   __device__ inline void issue(const LbPtrs& P, int64_t top_) {
     top = top_;
     const int l = lane_id();
+    int64_t lo = 0;
+    if constexpr (L2) lo = chunk() >= 1 ? (chunk() - 1) * int64_t(kL2Chunk) : 0;
 #pragma unroll
     for (int k = 0; k < W; k++) {
       const int64_t idx = top - kWave * k - l;
-      w0[k] = idx >= 0 ? ld_agent(P.rec + 2 * idx) : kStPfx;  // (index -1 acts as a zero prefix)
-      w1[k] = idx >= 0 ? ld_agent(P.rec + 2 * idx + 1) : kStPfx;
+      const bool in = idx >= lo;
+      // (index -1 acts as a zero prefix; past the chunk edge, an empty aggregate)
+      w0[k] = in ? ld_agent(P.rec + 2 * idx) : idx < 0 ? kStPfx : kStAgg;
+      w1[k] = in ? ld_agent(P.rec + 2 * idx + 1) : kStPfx;
+    }
+    if constexpr (L2) {
+      const int64_t c = chunk() - 2 - l;  // (chunk -1: the empty prefix before chunk 0)
+      this->c0 = c >= 0 ? ld_agent(P.l2 + 2 * c) : kStPfx;
+      this->c1 = c >= 0 ? ld_agent(P.l2 + 2 * c + 1) : kStPfx;
     }
   }
 };
@@ -348,9 +411,13 @@ struct LbWindows {
 // Consume loaded windows: accumulate per-lane partial sums into acc.  Returns
 // true when the walk reached an inclusive prefix; otherwise *next_top is where
 // to continue and *wait_idx >= 0 names a predecessor that has not published.
-template <int W>
-__device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWindows<W>& G, uint64_t acc[kNumComp],
-                                  int64_t* next_top, int64_t* wait_idx, uint32_t* spins, bool* timed_out) {
+// L2: once the level-1 windows are consumed down to their chunk edge, the
+// contiguous run of chunk records that are there is added; a chunk prefix ends
+// the resolve, the first absent chunk record is where level 1 goes on.  A chunk
+// record is never waited for.
+template <int W, bool L2>
+__device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWindows<W, L2>& G, uint64_t acc[kNumComp],
+                                  int64_t* next_top, int64_t* wait_idx, uint32_t* spins, bool* timed_out, LbDiag* D) {
   const int l = lane_id();
   int64_t top = G.top;
   *wait_idx = -1;
@@ -368,6 +435,7 @@ __device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWi
       *next_top = top;
       return false;
     }
+    LBDIAG(D->recs += __builtin_popcountll(__ballot(l <= first && idx >= 0 && (G.w0[k] != kStAgg))));
     uint64_t c[kNumComp] = {0, 0, 0, 0};
     if (l < first && state == kStAgg) {
 #pragma unroll
@@ -392,27 +460,76 @@ __device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWi
     if (first < 64) return true;
     top -= kWave;
   }
+  if constexpr (L2) {
+    // (chunks 0 and 1 reach index -1 inside the level-1 windows)
+    const int64_t ck = G.chunk();
+    if (ck >= 2) {
+      const uint64_t s0 = G.c0 & kStMask, s1 = G.c1 & kStMask;
+      // both halves of one store: a record caught between its Agg and its Pfx
+      // store reads as absent
+      const bool there = s0 == s1 && (s0 == kStAgg || s0 == kStPfx);
+      const uint64_t pfxm = __ballot(there && s0 == kStPfx), absent = __ballot(!there);
+      const int firstp = pfxm ? __builtin_ctzll(pfxm) : 64, firsta = absent ? __builtin_ctzll(absent) : 64;
+      const bool ends = firstp < firsta;
+      if (ends ? l <= firstp : l < firsta) {
+        acc[0] += G.c0 & ((1ull << kPfBits[0]) - 1);
+        acc[1] += (G.c0 >> kPfBits[0]) & ((1ull << kPfBits[1]) - 1);
+        acc[2] += G.c1 & ((1ull << kPfBits[2]) - 1);
+        acc[3] += (G.c1 >> kPfBits[2]) & ((1ull << kPfBits[3]) - 1);
+      }
+      LBDIAG(D->recs2 += ends ? firstp + (ck - 2 - firstp >= 0) : firsta);
+      if (ends) return true;
+      // (chunk -1 reads as a prefix, so the first absent chunk is >= 0)
+      top = (ck - 2 - firsta) * int64_t(kL2Chunk) + (kL2Chunk - 1);
+    }
+  }
   *next_top = top;
   return false;
 }
 
 // Finish a resolve whose first windows (from v-1 down) are already loaded.
-template <int W>
+// L2: the wave that resolves a chunk's last block publishes the chunk's record:
+// the summed aggregates as soon as its first window shows the chunk's 63 others
+// as packed aggregates (before it walks on), the chunk's inclusive prefix with
+// its own.  Neither is ever waited for by anyone.
+// WL: the windows of every later round trip (a long walk's trips are not in
+// the shadow of an emit step's loads, as the first one is).
+template <int W, bool L2, int WL = W>
 __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, const uint64_t agg[kNumComp],
-                                 uint64_t excl[kNumComp], uint32_t* timeout_flag, const LbWindows<W>& first_win) {
+                                 uint64_t excl[kNumComp], uint32_t* timeout_flag, const LbWindows<W, L2>& first_win,
+                                 LbDiag* D = nullptr) {
   const int l = lane_id();
   const LbPtrs P(st, n_blocks);
   uint64_t acc[kNumComp] = {0, 0, 0, 0};
   uint32_t spins = 0;
   bool timed_out = false;
   int64_t top = int64_t(v) - 1, wait_idx = -1;
-  bool done = v == 0 || lb_consume(P, n_blocks, first_win, acc, &top, &wait_idx, &spins, &timed_out);
+  LBDIAG(LbDiag d0{0, 0, 0, 0}; if (!D) D = &d0; D->trips = v > 0; D->recs = D->recs2 = 0; D->poll = 0);
+  if constexpr (L2) {
+    if ((v & (kL2Chunk - 1)) == kL2Chunk - 1 && agg_packable(agg)) {
+      // lanes 0..62 of the first window: the chunk's other blocks
+      const uint64_t w = first_win.w0[0];
+      if (!__ballot(l < int(kL2Chunk) - 1 && (w & kStMask) != kStAgg)) {
+        const uint64_t m = l < int(kL2Chunk) - 1 ? w : 0;
+        // (64 packed aggregates: each sum stays under 2^32)
+        uint64_t s01 = ((m >> kPkShift[0]) & ((1ull << kPkBits[0]) - 1)) | ((m >> kPkShift[1]) & ((1ull << kPkBits[1]) - 1)) << 32;
+        uint64_t s23 = ((m >> kPkShift[2]) & ((1ull << kPkBits[2]) - 1)) | ((m >> kPkShift[3]) & ((1ull << kPkBits[3]) - 1)) << 32;
+        s01 = wave_sum(s01);
+        s23 = wave_sum(s23);
+        const uint64_t ca[kNumComp] = {(s01 & 0xffffffffu) + agg[0], (s01 >> 32) + agg[1], (s23 & 0xffffffffu) + agg[2],
+                                       (s23 >> 32) + agg[3]};
+        if (l == 0) l2_store(P, v / kL2Chunk, kStAgg, ca);
+      }
+    }
+  }
+  bool done = v == 0 || lb_consume(P, n_blocks, first_win, acc, &top, &wait_idx, &spins, &timed_out, D);
   // a lane polling a wide record may have timed out on its own: leave together
   if (__ballot(timed_out)) timed_out = true;
   while (!done && !timed_out) {
     if (wait_idx >= 0) {
       // Poll the missing predecessor from ONE lane (a whole-window re-read per
       // poll would flood this CU's memory queue), then re-read the windows.
+      LBDIAG(const uint64_t tp = __builtin_amdgcn_s_memtime());
       if (l == 0) {
         while ((ld_agent(P.rec + 2 * wait_idx) & kStMask) == 0) {
           if (++spins > (1u << 22)) { timed_out = true; break; }
@@ -420,10 +537,12 @@ __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, co
         }
       }
       if (__shfl(timed_out ? 1 : 0, 0, kWave)) { timed_out = true; break; }
+      LBDIAG(D->poll += __builtin_amdgcn_s_memtime() - tp);
     }
-    LbWindows<W> G;
+    LbWindows<WL, L2> G;
     G.issue(P, top);
-    done = lb_consume(P, n_blocks, G, acc, &top, &wait_idx, &spins, &timed_out);
+    LBDIAG(D->trips++);
+    done = lb_consume(P, n_blocks, G, acc, &top, &wait_idx, &spins, &timed_out, D);
     if (__ballot(timed_out)) timed_out = true;
   }
   if (timed_out && l == 0) g_atomic_or(timeout_flag, 1u << PBL_TIMEOUT);
@@ -434,21 +553,26 @@ __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, co
 #pragma unroll
     for (int q = 0; q < kNumComp; q++) p[q] = excl[q] + agg[q];
     lb_store_pfx(P, n_blocks, v, p);
+    if constexpr (L2) {
+      if ((v & (kL2Chunk - 1)) == kL2Chunk - 1 && !timed_out && pfx_packable(p) && l == 0)
+        l2_store(P, v / kL2Chunk, kStPfx, p);
+    }
   }
 }
 
-template <int W = kLbWin>
+template <int W = kLbWin, bool L2 = false>
 __device__ inline void lb_resolve(uint64_t* st, uint32_t n_blocks, uint32_t v, const uint64_t agg[kNumComp],
                                   uint64_t excl[kNumComp], uint32_t* timeout_flag) {
-  LbWindows<W> G;
+  LbWindows<W, L2> G;
   if (v > 0) G.issue(LbPtrs(st, n_blocks), int64_t(v) - 1);
   lb_finish(st, n_blocks, v, agg, excl, timeout_flag, G);
 }
 
+template <bool L2 = false>
 __device__ inline void lookback(uint64_t* st, uint32_t n_blocks, uint32_t v, const uint64_t agg[kNumComp],
                                 uint64_t excl[kNumComp], uint32_t* timeout_flag) {
   lb_publish(st, n_blocks, v, agg);
-  lb_resolve(st, n_blocks, v, agg, excl, timeout_flag);
+  lb_resolve<kLbWin, L2>(st, n_blocks, v, agg, excl, timeout_flag);
 }
 
 // ---- shared by the row and colblk decoders --------------------------------

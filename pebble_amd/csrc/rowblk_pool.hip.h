@@ -94,6 +94,29 @@ namespace pool {
 #ifndef PBL_POOL_PREFETCH_LATE
 #define PBL_POOL_PREFETCH_LATE 1
 #endif
+// PBL_POOL_LB_WIN / PBL_POOL_LB_WIN_LATER: windows of 64 predecessor records
+// the emit loads with its first step, and per later round trip of the same
+// resolve (this kernel's own counts: the other kernels keep PBL_LB_WIN for
+// both).  Round 9's stamps: 94 % of config 2's resolves take two round trips
+// and meet the prefix 130 records back, i.e. within the second trip's first
+// records, so a later trip of 128 records loads 120 it never needs, and every
+// record is an 8-byte agent-scope load of lines that some 2000 waves read and
+// write.  Plain bench.py, GiB/s, parent / first-later (DESIGN.md 3.1, round 9,
+// profiles/r09/ab_variants.txt):
+//   config 2      1379-1380 / 2-1: 1469-1471, 3-1: 1517-1521, 4-1: 1477-1479
+//   zipf on pool   933-943  / 2-1: 955, 3-1: 921-923, 4-1: 902-907
+// 2-1 is the one form under which no measured workload falls below its
+// parent's range; with first = later config 2 gives 3: 1438-1444, 4: 1485-1488,
+// 5: 1318-1340, 6: 1235-1239, 8: 1172-1174.
+#ifndef PBL_POOL_LB_WIN
+#define PBL_POOL_LB_WIN PBL_LB_WIN
+#endif
+#ifndef PBL_POOL_LB_WIN_LATER
+#define PBL_POOL_LB_WIN_LATER 1
+#endif
+constexpr int kPoolLbWin = PBL_POOL_LB_WIN;
+// (the two-level form's windows must reach the chunk edge: it keeps the first count)
+constexpr int kPoolLbWinLater = kLbL2 ? kPoolLbWin : PBL_POOL_LB_WIN_LATER;
 constexpr int kEarlyRel = PBL_POOL_EARLYREL;
 constexpr uint32_t kPrefetch = PBL_POOL_PREFETCH;
 constexpr int kNW = PBL_POOL_WAVES;      // waves per workgroup (one workgroup per CU)
@@ -1185,7 +1208,7 @@ __device__ __noinline__ void block_slow(Stage& S, uint8_t* keybuf, uint32_t keyc
   }
   const bool okk = ss.status == PBL_OK;
   const uint64_t agg[kNumComp] = {okk ? ss.nkv : 0, okk ? ss.kb : 0, okk ? ss.vb : 0, okk ? ss.nr : 0};
-  lookback(lb_state, nb, b, agg, excl, &O.totals->status_mask);
+  lookback<kLbL2>(lb_state, nb, b, agg, excl, &O.totals->status_mask);
   uint32_t st2 = ss.status;
   if (okk && overflows(O, excl, agg)) st2 = PBL_OVERFLOW;
   if (st2 == PBL_OK) slow_walk(src, from_lds, blen, flags, A.in.synthetic_seq_num, keybuf, keycap, kPassAll, O, b, excl, &ss);
@@ -1214,7 +1237,7 @@ __device__ __noinline__ void block_big(const Args A, uint32_t b, uint64_t boff, 
                                   okk ? to_glb(O.blk_val_base)[b] : 0,
                                   okk ? uint64_t(GlbBlk{to_glb(A.in.blocks + boff), blen}.le32(blen - 4)) : 0};
   uint64_t excl[kNumComp];
-  lb_resolve(lb_state, nb, b, agg, excl, &O.totals->status_mask);
+  lb_resolve<kLbWin, kLbL2>(lb_state, nb, b, agg, excl, &O.totals->status_mask);
   uint32_t st2 = st0;
   if (okk && overflows(O, excl, agg)) st2 = PBL_OVERFLOW;
   if (l == 0) {
@@ -1414,7 +1437,7 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   const uint32_t nkv = P.nkv, nres = P.nres;
   // the look-back windows, the first key batch, the first value step and the
   // first restart words: all in one round trip
-  LbWindows<kLbWin> G;
+  LbWindows<kPoolLbWin, kLbL2> G;
   if (b > 0) G.issue(LbPtrs(lb_state, nb), int64_t(b) - 1);
   KBatch K;
   VBatch VB, VB1;
@@ -1431,7 +1454,19 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   }
   const uint64_t agg[kNumComp] = {nkv, P.tkb, P.tvb, nres};
   uint64_t excl[kNumComp];
-  lb_finish(lb_state, nb, b, agg, excl, &O.totals->status_mask, G);
+#ifdef PBL_STAMPS
+  LbDiag LD;
+  lb_finish<kPoolLbWin, kLbL2, kPoolLbWinLater>(lb_state, nb, b, agg, excl, &O.totals->status_mask, G, &LD);
+  if (l == 0) {  // slots 11-14: what the resolve cost (counts, not times)
+    uint64_t* sp = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(O.workspace) + ws_bytes(nb)) + uint64_t(b) * 16;
+    sp[11] = LD.trips;
+    sp[12] = LD.recs;
+    sp[13] = LD.poll;
+    sp[14] = LD.recs2;
+  }
+#else
+  lb_finish<kPoolLbWin, kLbL2, kPoolLbWinLater>(lb_state, nb, b, agg, excl, &O.totals->status_mask, G);
+#endif
   PSTAMP(A, b, 5, l == 0);
   uint32_t status = P.status;
   if (ok0 && overflows(O, excl, agg)) status = PBL_OVERFLOW;
@@ -1560,7 +1595,17 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
 //    emit never waits for a stage: every stage holder runs on to its publish
 //    and its release without needing any other wave to move;
 //  - the look-back waits only on smaller tickets, each held by a wave that
-//    holds a stage (and so reaches its publish by the above) or has published.
+//    holds a stage (and so reaches its publish by the above) or has published;
+//    every poll of it (lb_finish's single-lane poll, lb_poll) is bounded by the
+//    spin cap and ends in PBL_TIMEOUT;
+//  - the two-level form (PBL_LB_L2) adds two stores and no wait: the wave that
+//    resolves a chunk's last block stores the chunk's summed aggregate after
+//    its first window (only from records it has already loaded) and the
+//    chunk's prefix with its own; a resolve reads chunk records in the round
+//    trip it makes anyway and never polls one: an absent, half-written or
+//    never-written record (a wide aggregate, a last block that another kernel
+//    resolves) costs exactly the one-level walk over that chunk's block
+//    records, so the four points above stand unchanged.
 // `ids` (mixed batches): the ascending ids of the batch's row blocks, their
 // count at workspace header word kWsRowCount; the colblk blocks' aggregates are
 // published before this launch (mixed_col_size_kernel), so the look-back walks

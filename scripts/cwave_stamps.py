@@ -23,7 +23,7 @@ print("blocks: len median", np.median(lens), "p90", np.percentile(lens, 90), "ma
 for _ in range(3):
     out = decode(b)
 torch.cuda.synchronize()
-ws_state = 256 + 10 * nb * 8
+ws_state = 256 + 10 * nb * 8 + 16 * ((nb + 63) // 64)
 st = out.workspace[ws_state: ws_state + nb * 16 * 8].view(torch.int64).view(nb, 16).cpu().numpy()
 for nm, a, z in [("stage", 0, 1), ("parse + rows", 1, 2), ("look-back", 2, 3), ("meta", 3, 4),
                  ("per-row arrays", 4, 5), ("keys", 5, 6), ("values", 6, 7), ("total", 0, 7)]:

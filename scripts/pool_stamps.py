@@ -5,7 +5,10 @@ wave's loop iteration starts (the end of the emit before), 0 stage acquired +
 ticket taken by the loop, 10 the same by the prefetch of the emit before (the
 DMA issued), 1 descriptor read, 2 staged (DMA landed), 3 walk + scan + publish,
 9 stage released, 4 metadata + value buckets, 5 look-back resolved, 6 keys /
-per-KV arrays written, 7 values done.  A block carries stamp 0 or stamp 10,
+per-KV arrays written, 7 values done; 11-14 are counts of the block's look-back
+resolve, not times: round trips (the first included), block records consumed,
+cycles in the single-lane poll on an unpublished predecessor, chunk records
+consumed (PBL_LB_L2).  A block carries stamp 0 or stamp 10,
 whichever way its stage was taken (a workspace reused from an earlier launch
 may hold both: the later one counts).  A build from before stamp 9 released
 the stage at 4.
@@ -32,11 +35,11 @@ else:
 b = BlockBatch.from_host(buf, off, lens, "cuda", N.PBL_FMT_ROW, N.PBL_KERNEL_POOL)
 for _ in range(3):
     out = decode(b)
-    ws_state = 256 + 10 * nb * 8
+    ws_state = 256 + 10 * nb * 8 + 16 * ((nb + 63) // 64)
     out.workspace[ws_state: ws_state + nb * 16 * 8].zero_()  # (the next launch may get this memory again)
 out = decode(b)
 torch.cuda.synchronize()
-ws_state = 256 + 10 * nb * 8
+ws_state = 256 + 10 * nb * 8 + 16 * ((nb + 63) // 64)
 st = out.workspace[ws_state: ws_state + nb * 16 * 8].view(torch.int64).view(nb, 16).cpu().numpy().copy()
 
 
@@ -68,6 +71,19 @@ m = (st[:, 8] > 0) & (st[:, 2] > st[:, 8])
 show("idle gap (emit end -> walk start)", st[m, 2] - st[m, 8])
 for nm, sel in (("  idle gap, prefetched", m & pre), ("  idle gap, loop-acquired", m & ~pre)):
     show(nm, st[sel, 2] - st[sel, 8])
+# the look-back resolve per block (counts, slots 11-14; the poll in cycles)
+lb = st[:, 11] > 0
+for nm, col in (("look-back round trips", 11), ("look-back block records consumed", 12),
+                ("look-back chunk records consumed", 14), ("look-back poll (unpublished pred.)", 13)):
+    d = st[lb, col].astype(np.float64)
+    if d.size:
+        print(f"{nm:34s} median {np.median(d):9.1f} mean {np.mean(d):9.2f} p90 {np.percentile(d, 90):9.1f}"
+              f"  ({d.size} blocks)")
+if lb.any():
+    trips = st[lb, 11]
+    print("round trips per resolve, share of blocks: " +
+          ", ".join(f"{k}: {100.0 * (trips == k).mean():.1f} %" for k in range(1, 6)) +
+          f", more: {100.0 * (trips > 5).mean():.1f} %;  resolves that polled: {100.0 * (st[lb, 13] > 0).mean():.1f} %")
 t0, t7 = st[:, 8][st[:, 8] > 0], st[:, 7][st[:, 7] > 0]
 print(f"kernel span {t7.max() - t0.min():.0f} cycles; blocks per CU {nb / 256:.0f}; "
       f"cycles per block per CU {(t7.max() - t0.min()) / (nb / 256):.0f}")

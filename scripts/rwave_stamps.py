@@ -33,7 +33,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 # one more launch with the stamp words cleared, timed by HIP events (the
 # s_memtime clock against wall time)
-ws_stamps = 256 + 10 * nb * 8
+ws_stamps = 256 + 10 * nb * 8 + 16 * ((nb + 63) // 64)
 out.workspace[ws_stamps: ws_stamps + nb * 16 * 8].zero_()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
@@ -41,7 +41,7 @@ decode_into(b, out)
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1)
-ws_state = 256 + 10 * nb * 8
+ws_state = 256 + 10 * nb * 8 + 16 * ((nb + 63) // 64)
 st = out.workspace[ws_state: ws_state + nb * 16 * 8].view(torch.int64).view(nb, 16).cpu().numpy()
 nkv = np.diff(out.blk_kv_base.cpu().numpy())[:nb]
 for nm, a, z in [("bases + meta", 0, 1), ("stage (DMA)", 1, 2), ("LDS walk", 2, 3), ("global walk", 3, 4), ("keys (wave 0)", 3, 5), ("values (wave 1)", 3, 6), ("long keys (wave 2)", 3, 7),
