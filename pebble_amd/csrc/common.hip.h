@@ -61,6 +61,14 @@ constexpr bool kLbL2 = PBL_LB_L2 != 0;
 // R2 granules).  A resolve normally costs ONE round trip: the windows of
 // predecessor records carry packed inclusive prefixes, so the nearest one ends
 // the walk without a second fetch.
+// The 16-byte forms (kLbV16, kLbSt16: the row pool kernel and the blocks it
+// hands on; every other kernel keeps the 8-byte accesses): a record read as ONE
+// 16-byte sc1 buffer load per lane, a packed prefix written as ONE 16-byte sc1
+// store.  rec[] is 16-byte aligned: the workspace is (pebble_amd.h) and
+// kWsHeader is a multiple of 16.  Nothing depends on a 16-byte access being
+// atomic: the halves stay self-tagged, and every torn combination is a state
+// the 8-byte reader already handles (w0 still Agg with w1 already Pfx: the
+// valid aggregate; w0 Pfx with w1 not yet Pfx: w1 is polled).
 constexpr uint64_t kKindInvalidTrailer = 191u;  // base.InternalKeyKindInvalid, seq 0
 
 // blockiter.SyntheticSeqNum fused into the decode (pbl_block_batch.
@@ -73,6 +81,7 @@ __device__ __forceinline__ uint64_t with_seq(uint64_t tr, uint64_t seq, uint32_t
 }
 
 constexpr uint64_t kWsHeader = 256;
+static_assert(kWsHeader % 16 == 0, "rec[] is read and written 16 bytes at a time");
 constexpr int kWsColTick = 2;   // header u32 [2]: the colblk queue's ticket counter (mixed batches)
 constexpr int kWsRowCount = 3;  // header u32 [3]: row-format blocks in a mixed batch
 constexpr uint32_t kSplitChunk = 4096;  // blocks per chunk of the mixed-batch split
@@ -276,6 +285,24 @@ __device__ inline bool pfx_packable(const uint64_t p[kNumComp]) {
          p[3] < (1ull << kPfBits[3]);
 }
 
+// Look-back forms (template flags; 0 is the 8-byte form, instruction for
+// instruction what every kernel but the row pool kernel runs).
+constexpr int kLbV16 = 1;   // a window's records as one 16-byte load per lane
+constexpr int kLbSt16 = 2;  // a packed prefix as one 16-byte store
+
+// A raw buffer over [p, p + bytes) (wave-uniform); offsets past it read as zero.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t lb_rsrc(const uint64_t* p, uint32_t bytes) {
+  const uint64_t a = reinterpret_cast<uint64_t>(p);
+  // (the builtin returns a signed int: through uint32_t, or a low word with
+  // bit 31 set would sign-extend over the high word)
+  const uint32_t alo = uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a)));
+  const uint32_t ahi = uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a >> 32)));
+  const uint64_t u = uint64_t(alo) | uint64_t(ahi) << 32;
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), 0, __builtin_amdgcn_readfirstlane(bytes),
+                                           0x00020000);
+}
+constexpr int kAuxSc1 = 16;  // the buffer builtins' cache policy: sc1 alone, as an agent-scope relaxed atomic's
+
 struct LbPtrs {
   uint64_t* rec;   // [2 * n_blocks]
   uint64_t* pfx;   // [kNumComp * n_blocks]
@@ -305,13 +332,22 @@ struct LbDiag {};
 #endif
 
 // Store block v's inclusive prefix `p` (lanes 0-3 of the calling wave).
+// kLbSt16: a packed prefix as one single-lane 16-byte sc1 store (one fabric
+// write instead of two); should it ever tear, the reader's poll of w1 covers it.
+template <int F = 0>
 __device__ inline void lb_store_pfx(const LbPtrs& P, uint32_t n_blocks, uint32_t v, const uint64_t p[kNumComp]) {
   const int l = lane_id();
   if (pfx_packable(p)) {
     if (l == 0) {
-      // w1 first: a reader that sees w0's Pfx before w1's polls w1
-      st_agent(P.rec + 2ull * v + 1, kStPfx | p[2] | (p[3] << kPfBits[2]));
-      st_agent(P.rec + 2ull * v, kStPfx | p[0] | (p[1] << kPfBits[0]));
+      if constexpr (F & kLbSt16) {
+        const uint64_t x0 = kStPfx | p[0] | (p[1] << kPfBits[0]), x1 = kStPfx | p[2] | (p[3] << kPfBits[2]);
+        const u32x4 x = {uint32_t(x0), uint32_t(x0 >> 32), uint32_t(x1), uint32_t(x1 >> 32)};
+        __builtin_amdgcn_raw_buffer_store_b128(x, lb_rsrc(P.rec + 2ull * v, 16), 0, 0, kAuxSc1);
+      } else {
+        // w1 first: a reader that sees w0's Pfx before w1's polls w1
+        st_agent(P.rec + 2ull * v + 1, kStPfx | p[2] | (p[3] << kPfBits[2]));
+        st_agent(P.rec + 2ull * v, kStPfx | p[0] | (p[1] << kPfBits[0]));
+      }
     }
   } else {
     if (l < kNumComp) {
@@ -370,6 +406,13 @@ __device__ inline void lb_fetch4(uint64_t* src, uint32_t n_blocks, int64_t idx, 
 
 // Windows of predecessor records loaded in one round trip: lane l of window k
 // holds rec[top - 64k - l] (w0 and w1).
+// F & kLbV16: one 16-byte load per lane and window, split into w0 and w1, in
+// place of two 8-byte loads that each touch all eight lines of the window.
+// A buffer load over the trip's records (the resource is based on the trip's
+// lowest record, so the 32-bit offset holds for every n_blocks), sc1, its wait
+// counted by the compiler like any load's.
+// `lanes` (a partial trip, one window): only lanes below it hold records, the
+// others an empty aggregate, and the walk goes on at top - lanes.
 // L2 (two-level form): the windows stop at the start of the chunk before
 // (top + 1)'s, 64..127 records (a lane past that edge holds an empty
 // aggregate), and lane l of one more window holds the record of chunk
@@ -380,25 +423,47 @@ template <>
 struct LbChunkWin<true> {
   uint64_t c0, c1;
 };
-template <int W, bool L2 = false>
+template <int W, bool L2 = false, int F = 0>
 struct LbWindows : LbChunkWin<L2> {
   static_assert(!L2 || W >= 2, "two windows reach the chunk edge");
   uint64_t w0[W], w1[W];
   int64_t top;
+  int lanes;
   // the chunk of block top + 1
   __device__ inline int64_t chunk() const { return (top + 1) >> 6; }
-  __device__ inline void issue(const LbPtrs& P, int64_t top_) {
+  __device__ inline void issue(const LbPtrs& P, int64_t top_, int lanes_ = kWave) {
     top = top_;
+    lanes = lanes_;
     const int l = lane_id();
     int64_t lo = 0;
     if constexpr (L2) lo = chunk() >= 1 ? (chunk() - 1) * int64_t(kL2Chunk) : 0;
+    if constexpr (F & kLbV16) {
+      // the trip's records [base, top]: top >= 0 whenever a trip is issued
+      const int64_t low = top - int64_t(kWave) * W + 1, base = low > lo ? low : lo;
+      const __amdgpu_buffer_rsrc_t rs = lb_rsrc(P.rec + 2 * base, uint32_t(top - base + 1) * 16u);
 #pragma unroll
-    for (int k = 0; k < W; k++) {
-      const int64_t idx = top - kWave * k - l;
-      const bool in = idx >= lo;
-      // (index -1 acts as a zero prefix; past the chunk edge, an empty aggregate)
-      w0[k] = in ? ld_agent(P.rec + 2 * idx) : idx < 0 ? kStPfx : kStAgg;
-      w1[k] = in ? ld_agent(P.rec + 2 * idx + 1) : kStPfx;
+      for (int k = 0; k < W; k++) {
+        const int64_t idx = top - kWave * k - l;
+        const bool in = idx >= lo && l < lanes;
+        // (a select, not the range check's zero: that would read as "not published")
+        // (a lane past a partial trip's records is an empty aggregate even
+        // below index 0: the zero prefix must not end the walk over records
+        // the trip did not load)
+        const uint64_t o0 = idx < 0 && l < lanes ? kStPfx : kStAgg;
+        u32x4 x = {uint32_t(o0), uint32_t(o0 >> 32), 0u, uint32_t(kStPfx >> 32)};
+        if (in) x = __builtin_amdgcn_raw_buffer_load_b128(rs, uint32_t(idx - base) * 16u, 0, kAuxSc1);
+        w0[k] = x[0] | uint64_t(x[1]) << 32;
+        w1[k] = x[2] | uint64_t(x[3]) << 32;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < W; k++) {
+        const int64_t idx = top - kWave * k - l;
+        const bool in = idx >= lo && l < lanes;
+        // (index -1 acts as a zero prefix; past the chunk edge, an empty aggregate)
+        w0[k] = in ? ld_agent(P.rec + 2 * idx) : idx < 0 && l < lanes ? kStPfx : kStAgg;
+        w1[k] = in ? ld_agent(P.rec + 2 * idx + 1) : kStPfx;
+      }
     }
     if constexpr (L2) {
       const int64_t c = chunk() - 2 - l;  // (chunk -1: the empty prefix before chunk 0)
@@ -415,8 +480,8 @@ struct LbWindows : LbChunkWin<L2> {
 // contiguous run of chunk records that are there is added; a chunk prefix ends
 // the resolve, the first absent chunk record is where level 1 goes on.  A chunk
 // record is never waited for.
-template <int W, bool L2>
-__device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWindows<W, L2>& G, uint64_t acc[kNumComp],
+template <int W, bool L2, int F>
+__device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWindows<W, L2, F>& G, uint64_t acc[kNumComp],
                                   int64_t* next_top, int64_t* wait_idx, uint32_t* spins, bool* timed_out, LbDiag* D) {
   const int l = lane_id();
   int64_t top = G.top;
@@ -458,7 +523,7 @@ __device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWi
 #pragma unroll
     for (int q = 0; q < kNumComp; q++) acc[q] += c[q];
     if (first < 64) return true;
-    top -= kWave;
+    top -= W == 1 ? G.lanes : kWave;  // (a partial trip is one window)
   }
   if constexpr (L2) {
     // (chunks 0 and 1 reach index -1 inside the level-1 windows)
@@ -494,10 +559,15 @@ __device__ inline bool lb_consume(const LbPtrs& P, uint32_t n_blocks, const LbWi
 // its own.  Neither is ever waited for by anyone.
 // WL: the windows of every later round trip (a long walk's trips are not in
 // the shadow of an emit step's loads, as the first one is).
-template <int W, bool L2, int WL = W>
+// LL < 64 (with WL 1): the first later trip loads only the LL records below
+// top (the median resolve meets its prefix within the first few of them); a
+// trip after a partial one that found no prefix is a full window again, and so
+// on in turn, so a long walk costs at most one extra trip per two.
+template <int W, bool L2, int WL = W, int F = 0, int LL = kWave>
 __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, const uint64_t agg[kNumComp],
-                                 uint64_t excl[kNumComp], uint32_t* timeout_flag, const LbWindows<W, L2>& first_win,
+                                 uint64_t excl[kNumComp], uint32_t* timeout_flag, const LbWindows<W, L2, F>& first_win,
                                  LbDiag* D = nullptr) {
+  static_assert(LL == kWave || (WL == 1 && !L2 && LL > 0 && LL < kWave), "a partial trip is one window of the one-level form");
   const int l = lane_id();
   const LbPtrs P(st, n_blocks);
   uint64_t acc[kNumComp] = {0, 0, 0, 0};
@@ -525,6 +595,7 @@ __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, co
   bool done = v == 0 || lb_consume(P, n_blocks, first_win, acc, &top, &wait_idx, &spins, &timed_out, D);
   // a lane polling a wide record may have timed out on its own: leave together
   if (__ballot(timed_out)) timed_out = true;
+  bool part = LL < kWave;
   while (!done && !timed_out) {
     if (wait_idx >= 0) {
       // Poll the missing predecessor from ONE lane (a whole-window re-read per
@@ -539,11 +610,17 @@ __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, co
       if (__shfl(timed_out ? 1 : 0, 0, kWave)) { timed_out = true; break; }
       LBDIAG(D->poll += __builtin_amdgcn_s_memtime() - tp);
     }
-    LbWindows<WL, L2> G;
-    G.issue(P, top);
+    LbWindows<WL, L2, F> G;
+    if constexpr (LL < kWave) {
+      G.issue(P, top, part ? LL : kWave);
+    } else {
+      G.issue(P, top);
+    }
     LBDIAG(D->trips++);
     done = lb_consume(P, n_blocks, G, acc, &top, &wait_idx, &spins, &timed_out, D);
     if (__ballot(timed_out)) timed_out = true;
+    // (a trip that met an unpublished record is read again in the same form)
+    if (LL < kWave && wait_idx < 0) part = !part;
   }
   if (timed_out && l == 0) g_atomic_or(timeout_flag, 1u << PBL_TIMEOUT);
 #pragma unroll
@@ -552,7 +629,7 @@ __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, co
     uint64_t p[kNumComp];
 #pragma unroll
     for (int q = 0; q < kNumComp; q++) p[q] = excl[q] + agg[q];
-    lb_store_pfx(P, n_blocks, v, p);
+    lb_store_pfx<F>(P, n_blocks, v, p);
     if constexpr (L2) {
       if ((v & (kL2Chunk - 1)) == kL2Chunk - 1 && !timed_out && pfx_packable(p) && l == 0)
         l2_store(P, v / kL2Chunk, kStPfx, p);
@@ -560,19 +637,19 @@ __device__ inline void lb_finish(uint64_t* st, uint32_t n_blocks, uint32_t v, co
   }
 }
 
-template <int W = kLbWin, bool L2 = false>
+template <int W = kLbWin, bool L2 = false, int F = 0>
 __device__ inline void lb_resolve(uint64_t* st, uint32_t n_blocks, uint32_t v, const uint64_t agg[kNumComp],
                                   uint64_t excl[kNumComp], uint32_t* timeout_flag) {
-  LbWindows<W, L2> G;
+  LbWindows<W, L2, F> G;
   if (v > 0) G.issue(LbPtrs(st, n_blocks), int64_t(v) - 1);
-  lb_finish(st, n_blocks, v, agg, excl, timeout_flag, G);
+  lb_finish<W, L2, W, F>(st, n_blocks, v, agg, excl, timeout_flag, G);
 }
 
-template <bool L2 = false>
+template <bool L2 = false, int F = 0>
 __device__ inline void lookback(uint64_t* st, uint32_t n_blocks, uint32_t v, const uint64_t agg[kNumComp],
                                 uint64_t excl[kNumComp], uint32_t* timeout_flag) {
   lb_publish(st, n_blocks, v, agg);
-  lb_resolve<kLbWin, L2>(st, n_blocks, v, agg, excl, timeout_flag);
+  lb_resolve<kLbWin, L2, F>(st, n_blocks, v, agg, excl, timeout_flag);
 }
 
 // ---- shared by the row and colblk decoders --------------------------------

@@ -114,6 +114,36 @@ namespace pool {
 #ifndef PBL_POOL_LB_WIN_LATER
 #define PBL_POOL_LB_WIN_LATER 1
 #endif
+// PBL_LB_V16 / PBL_POOL_LB_ST16 / PBL_POOL_LB_LATER_LANES (round 10, DESIGN.md
+// 3.1): this kernel's look-back records as single 16-byte accesses (the blocks
+// handed to block_big / block_slow included; every other kernel keeps the
+// 8-byte form).
+//   PBL_LB_V16 1              a window is one 16-byte sc1 buffer load per lane
+//                             (8 line touches) instead of two 8-byte loads (16)
+//   PBL_POOL_LB_ST16 1        a packed prefix is one 16-byte sc1 store, not two
+//                             8-byte ones
+//   PBL_POOL_LB_LATER_LANES   64, 32 or 16: the records a resolve's first later
+//                             trip loads (the median resolve needs 1-9 of them);
+//                             a trip after a partial one that found no prefix is
+//                             a full window again.  Needs PBL_POOL_LB_WIN_LATER 1.
+// Per resolve (2 trips): 6 loads and 48 line touches before, 3 loads and 18-19
+// line touches now.  Plain bench.py, config 2, GiB/s, one box, one session,
+// parent 1509-1520 (profiles/r10/ab_variants.txt): each piece alone
+// V16 1581, ST16 1593, 16 lanes 1628; V16 + ST16 1636; with 32 lanes 1684;
+// all three at 16 lanes (shipped) 1700-1702; the same with a 3-window first
+// trip 1716, which gains on config 2, hide 4 and mixed and loses 2 % on
+// Zipf-sized blocks against 2-1 (above the parent everywhere): 2-1 stays.
+#ifndef PBL_LB_V16
+#define PBL_LB_V16 1
+#endif
+#ifndef PBL_POOL_LB_ST16
+#define PBL_POOL_LB_ST16 1
+#endif
+#ifndef PBL_POOL_LB_LATER_LANES
+#define PBL_POOL_LB_LATER_LANES 16
+#endif
+constexpr int kPoolLbF = (PBL_LB_V16 ? kLbV16 : 0) | (PBL_POOL_LB_ST16 ? kLbSt16 : 0);
+constexpr int kPoolLbLaterLanes = kLbL2 ? kWave : PBL_POOL_LB_LATER_LANES;
 constexpr int kPoolLbWin = PBL_POOL_LB_WIN;
 // (the two-level form's windows must reach the chunk edge: it keeps the first count)
 constexpr int kPoolLbWinLater = kLbL2 ? kPoolLbWin : PBL_POOL_LB_WIN_LATER;
@@ -1208,7 +1238,7 @@ __device__ __noinline__ void block_slow(Stage& S, uint8_t* keybuf, uint32_t keyc
   }
   const bool okk = ss.status == PBL_OK;
   const uint64_t agg[kNumComp] = {okk ? ss.nkv : 0, okk ? ss.kb : 0, okk ? ss.vb : 0, okk ? ss.nr : 0};
-  lookback<kLbL2>(lb_state, nb, b, agg, excl, &O.totals->status_mask);
+  lookback<kLbL2, kPoolLbF>(lb_state, nb, b, agg, excl, &O.totals->status_mask);
   uint32_t st2 = ss.status;
   if (okk && overflows(O, excl, agg)) st2 = PBL_OVERFLOW;
   if (st2 == PBL_OK) slow_walk(src, from_lds, blen, flags, A.in.synthetic_seq_num, keybuf, keycap, kPassAll, O, b, excl, &ss);
@@ -1237,7 +1267,7 @@ __device__ __noinline__ void block_big(const Args A, uint32_t b, uint64_t boff, 
                                   okk ? to_glb(O.blk_val_base)[b] : 0,
                                   okk ? uint64_t(GlbBlk{to_glb(A.in.blocks + boff), blen}.le32(blen - 4)) : 0};
   uint64_t excl[kNumComp];
-  lb_resolve<kLbWin, kLbL2>(lb_state, nb, b, agg, excl, &O.totals->status_mask);
+  lb_resolve<kLbWin, kLbL2, kPoolLbF>(lb_state, nb, b, agg, excl, &O.totals->status_mask);
   uint32_t st2 = st0;
   if (okk && overflows(O, excl, agg)) st2 = PBL_OVERFLOW;
   if (l == 0) {
@@ -1437,7 +1467,7 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   const uint32_t nkv = P.nkv, nres = P.nres;
   // the look-back windows, the first key batch, the first value step and the
   // first restart words: all in one round trip
-  LbWindows<kPoolLbWin, kLbL2> G;
+  LbWindows<kPoolLbWin, kLbL2, kPoolLbF> G;
   if (b > 0) G.issue(LbPtrs(lb_state, nb), int64_t(b) - 1);
   KBatch K;
   VBatch VB, VB1;
@@ -1456,7 +1486,7 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
   uint64_t excl[kNumComp];
 #ifdef PBL_STAMPS
   LbDiag LD;
-  lb_finish<kPoolLbWin, kLbL2, kPoolLbWinLater>(lb_state, nb, b, agg, excl, &O.totals->status_mask, G, &LD);
+  lb_finish<kPoolLbWin, kLbL2, kPoolLbWinLater, kPoolLbF, kPoolLbLaterLanes>(lb_state, nb, b, agg, excl, &O.totals->status_mask, G, &LD);
   if (l == 0) {  // slots 11-14: what the resolve cost (counts, not times)
     uint64_t* sp = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(O.workspace) + ws_bytes(nb)) + uint64_t(b) * 16;
     sp[11] = LD.trips;
@@ -1465,7 +1495,7 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
     sp[14] = LD.recs2;
   }
 #else
-  lb_finish<kPoolLbWin, kLbL2, kPoolLbWinLater>(lb_state, nb, b, agg, excl, &O.totals->status_mask, G);
+  lb_finish<kPoolLbWin, kLbL2, kPoolLbWinLater, kPoolLbF, kPoolLbLaterLanes>(lb_state, nb, b, agg, excl, &O.totals->status_mask, G);
 #endif
   PSTAMP(A, b, 5, l == 0);
   uint32_t status = P.status;
