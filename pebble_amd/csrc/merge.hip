@@ -10,7 +10,8 @@
 //   merge_persize_kernel  lane per result block: its status and its sizes, the
 //       sums of the runs' base differences
 //   merge_sum_kernel / merge_bases_kernel  the exclusive scan over result blocks
-//       (chunks of 256, as scan.hip's): bases, statuses, totals, the capacity check
+//       (result_core.hip.h's chunk_sums / bases): bases, statuses, totals, the
+//       capacity check
 //   merge_rank_kernel<comparer>  lane per source KV (run r, block q, index j): its
 //       place in result block q is j + the KVs of the runs before r that are <=
 //       it + the KVs of the runs after r that are < it (seek_core.hip.h's iupper /
@@ -21,9 +22,11 @@
 //       keys and values are contiguous in result order over the whole result, so
 //       a block-relative offset is the global prefix minus the block's base
 //   merge_emit_kernel  one wave per 64 result KVs: the per-KV arrays gathered
-//       through (run, kv), keys lane per KV in 16-B chunks, values of at most
-//       512 B 8 lanes per KV and longer ones by the whole wave
-//       (scan_emit_kernel's loops with an indexed source).
+//       through (run, kv), keys lane per KV in 16-B chunks, values by
+//       result_core.hip.h's copy_values.
+//
+// The tile scan, every block's last offset, the per-KV arrays and the value copy
+// are result_core.hip.h's too; the kernels here are wrappers around them.
 //
 // The ranks are a bijection onto the block's places when every run's block is
 // sorted, which the validation guarantees for every block that is merged; the
@@ -35,6 +38,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "result_core.hip.h"
 #include "seek_core.hip.h"
 
 namespace pbl {
@@ -45,6 +49,7 @@ constexpr uint64_t kHdr = 64;
 constexpr uint32_t kTileShift = 8, kTile = 1u << kTileShift;  // result KVs per tile
 constexpr int kMergeTPB = 256;
 constexpr uint32_t kChunk = 256;      // result blocks per chunk of the scan over blocks
+static_assert(kMergeTPB == result::kTPB && kChunk == uint32_t(result::kTPB), "result_core.hip.h's workgroup");
 constexpr uint32_t kGrid = 2048;      // workgroups of a grid-striding kernel, at most (per run)
 constexpr uint64_t kMaxBytes = 0xffffffffull;  // a block's key / value bytes (u32 offsets)
 constexpr uint64_t kMaxKvs = 0xffffffffull;    // a block's KVs
@@ -108,6 +113,7 @@ struct Ws {
     n_chunks = L.n_chunks;
   }
   __device__ gptr<uint64_t> q(int c) const { return q64 + uint64_t(c) * qs; }  // per-block KVs, key bytes, value bytes
+  __device__ result::Sizes sizes() const { return result::Sizes{q64, csum, qst, qs, n_chunks}; }
 };
 
 __device__ inline uint64_t run_held(const MergeArgs& A, uint32_t r) {
@@ -125,42 +131,9 @@ __device__ inline bool described(const MergeArgs& A) {
   return t <= A.n_kv;
 }
 
-// The block that owns KV index kv: the last b with base[b] <= kv (blocks that
-// own no KV index are stepped over).
-__device__ inline uint32_t block_of(gptr<const uint64_t> base, uint32_t nb, uint64_t kv) {
-  uint32_t lo = 0, hi = nb;
-  while (lo < hi) {
-    const uint32_t m = lo + (hi - lo) / 2;
-    if (base[m] <= kv) lo = m + 1;
-    else hi = m;
-  }
-  return lo ? lo - 1 : 0;
-}
-
-// Sum of v over the workgroup (every thread gets it).  `lds`: 4 words.
-__device__ inline uint64_t block_sum64(uint64_t v, uint64_t* lds) {
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane_id() == 0) lds[wave_id()] = v;
-  __syncthreads();
-  return lds[0] + lds[1] + lds[2] + lds[3];
-}
-// Exclusive scan of v over the workgroup; *total = the sum.  `lds`: 4 words.
-__device__ inline uint64_t block_excl_scan64(uint64_t v, uint64_t* lds, uint64_t* total) {
-  const uint64_t inc = wave_incl_scan(v);
-  __syncthreads();
-  if (lane_id() == kWave - 1) lds[wave_id()] = inc;
-  __syncthreads();
-  uint64_t before = 0, t = 0;
-  for (int w = 0; w < kMergeTPB / kWave; w++) {
-    const uint64_t s = lds[w];
-    if (w < wave_id()) before += s;
-    t += s;
-  }
-  *total = t;
-  return before + inc - v;
-}
-
+using result::block_excl_scan64;
+using result::block_of;
+using result::block_sum64;
 using GR = seek::GlobalReader;
 
 __device__ inline seek::View<GR> run_view(const MergeArgs& A, uint32_t r) {
@@ -222,12 +195,7 @@ __global__ __launch_bounds__(kMergeTPB) void merge_persize_kernel(MergeArgs A) {
 __global__ __launch_bounds__(kMergeTPB) void merge_sum_kernel(MergeArgs A) {
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, A.n_blocks, A.n_kv);
-  const uint64_t i = uint64_t(blockIdx.x) * kChunk + threadIdx.x;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const uint64_t s = block_sum64(i < A.n_blocks ? W.q(c)[i] : 0, lds);
-    if (threadIdx.x == 0) W.csum[uint64_t(c) * W.n_chunks + blockIdx.x] = s;
-  }
+  result::chunk_sums<3>(W.sizes(), A.n_blocks, lds);
 }
 
 // The result's bases, statuses and totals; the capacity check (the last chunk).
@@ -235,45 +203,10 @@ __global__ __launch_bounds__(kMergeTPB) void merge_sum_kernel(MergeArgs A) {
 __global__ __launch_bounds__(kMergeTPB) void merge_bases_kernel(MergeArgs A) {
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, A.n_blocks, A.n_kv);
-  const pbl_decode_out& O = A.out.result;
-  const uint32_t n = A.n_blocks;
-  const uint64_t i = uint64_t(blockIdx.x) * kChunk + threadIdx.x;
   uint64_t ex[3], end[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    uint64_t before = 0;
-    for (uint32_t ch = threadIdx.x; ch < blockIdx.x; ch += kMergeTPB) before += W.csum[uint64_t(c) * W.n_chunks + ch];
-    before = block_sum64(before, lds);
-    uint64_t tot;
-    ex[c] = before + block_excl_scan64(i < n ? W.q(c)[i] : 0, lds, &tot);
-    end[c] = before + tot;
-  }
-  if (i < n) {
-    to_glb(O.blk_kv_base)[i] = ex[0];
-    to_glb(O.blk_key_base)[i] = ex[1];
-    to_glb(O.blk_val_base)[i] = ex[2];
-    if (O.blk_rst_base) to_glb(O.blk_rst_base)[i] = 0;
-    const uint32_t st = W.qst[i];
-    to_glb(O.blk_status)[i] = st;
-    if (st != PBL_OK) {
-      g_atomic_or(&O.totals->status_mask, 1u << st);
-      g_atomic_add(&O.totals->n_bad_blocks, 1u);
-    }
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    to_glb(O.blk_kv_base)[n] = end[0];
-    to_glb(O.blk_key_base)[n] = end[1];
-    to_glb(O.blk_val_base)[n] = end[2];
-    if (O.blk_rst_base) to_glb(O.blk_rst_base)[n] = 0;
-    const gptr<pbl_totals> T = to_glb(O.totals);
-    T->n_kv = end[0];
-    T->key_bytes = end[1];
-    T->val_bytes = end[2];
-    T->n_restarts = 0;
-    const bool over = !A.size_only && (end[0] > O.kv_cap || end[1] > O.key_cap || end[2] > O.val_cap);
+  bool over;
+  if (result::bases<3>(W.sizes(), A.out.result, A.n_blocks, A.size_only != 0, lds, ex, end, &over))
     W.hdr[kHSkip] = (over || end[0] > A.n_kv) ? 1u : 0u;
-    if (over) g_atomic_or(&O.totals->status_mask, 1u << PBL_OVERFLOW);
-  }
 }
 
 // blockIdx.y = run.  The place of every source KV in its result block.
@@ -335,18 +268,7 @@ __global__ __launch_bounds__(kMergeTPB) void merge_tile_scan_kernel(MergeArgs A)
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, A.n_blocks, A.n_kv);
   if (W.hdr[kHSkip] != 0) return;
-  uint64_t carry[2] = {0, 0};
-  for (uint64_t t0 = 0; t0 < W.nt; t0 += kMergeTPB) {
-    const uint64_t t = t0 + threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-      const uint64_t v = t < W.nt ? W.tsum[c][t] : 0;
-      uint64_t tot;
-      const uint64_t ex = block_excl_scan64(v, lds, &tot);
-      if (t < W.nt) W.tsum[c][t] = carry[c] + ex;
-      carry[c] += tot;
-    }
-  }
+  result::tile_scan_inplace(W.tsum, W.nt, lds);
 }
 
 // key_off / val_off of the result: the prefix of the lengths in result order,
@@ -359,11 +281,7 @@ __global__ __launch_bounds__(kMergeTPB) void merge_offsets_kernel(MergeArgs A) {
   const uint32_t nb = A.n_blocks;
   const gptr<const uint64_t> okvb = to_glb((const uint64_t*)O.blk_kv_base), okeyb = to_glb((const uint64_t*)O.blk_key_base),
                              ovalb = to_glb((const uint64_t*)O.blk_val_base);
-  for (uint64_t q = uint64_t(blockIdx.x) * kMergeTPB + threadIdx.x; q < nb; q += uint64_t(gridDim.x) * kMergeTPB) {
-    const uint64_t at = okvb[q + 1] + q;
-    to_glb(O.key_off)[at] = uint32_t(okeyb[q + 1] - okeyb[q]);
-    to_glb(O.val_off)[at] = uint32_t(ovalb[q + 1] - ovalb[q]);
-  }
+  result::last_offsets(O, nb, ~0ull);
   const uint64_t total = okvb[nb];
   for (uint64_t t = blockIdx.x; t < W.nt; t += gridDim.x) {
     const uint64_t p = (t << kTileShift) + threadIdx.x;
@@ -380,7 +298,7 @@ __global__ __launch_bounds__(kMergeTPB) void merge_offsets_kernel(MergeArgs A) {
 }
 
 #ifndef PBL_MERGE_EMIT_WAVES
-#define PBL_MERGE_EMIT_WAVES 5  // as scan_emit_kernel: the same copy loops
+#define PBL_MERGE_EMIT_WAVES 5  // as every caller of result::copy_values
 #endif
 __global__ void __launch_bounds__(kMergeTPB) __attribute__((amdgpu_waves_per_eu(PBL_MERGE_EMIT_WAVES)))
 merge_emit_kernel(MergeArgs A) {
@@ -424,62 +342,27 @@ merge_emit_kernel(MergeArgs A) {
         vdst = to_glb(O.val_bytes) + (ovalb[q] + vo);
       }
       if (ok) {
-        to_glb(O.trailer)[p] = to_glb(I.trailer)[kv];
-        if (O.kv_flags) to_glb(O.kv_flags)[p] = I.kv_flags ? to_glb(I.kv_flags)[kv] : uint8_t(0);
-        if (O.entry_off) to_glb(O.entry_off)[p] = I.entry_off ? to_glb(I.entry_off)[kv] : 0u;
-        if (O.tiering_span_id) {  // KVMeta travels with its KV
-          to_glb(O.tiering_span_id)[p] = I.tiering_span_id ? to_glb(I.tiering_span_id)[kv] : 0ull;
-          to_glb(O.tiering_attr)[p] = I.tiering_attr ? to_glb(I.tiering_attr)[kv] : 0ull;
-        }
+        result::copy_kv_arrays(O, p, I, kv, 0xff, true);
         if (A.out.src_run) to_glb(A.out.src_run)[p] = uint8_t(r);
         if (A.out.src_kv) to_glb(A.out.src_kv)[p] = kv;
         copy_chunks(kdst, ksrc, klen);
       }
     }
-    // values of at most 512 B: 8 lanes per KV (lane c of a group copies the
-    // value's 16-B chunks c, c + 8, ...); longer ones by the whole wave
-    // (scan_emit_kernel's two forms and its threshold)
-#pragma unroll 1
-    for (uint32_t u = 0; u < kWave / 8; u++) {
-      const int sl = int(8 * u + (lane >> 3));
-      const bool sv = __shfl(int(ok && vlen <= 512), sl, kWave) != 0;
-      const gptr<const uint8_t> sp = (gptr<const uint8_t>)__shfl((unsigned long long)vsrc, sl, kWave);
-      const gptr<uint8_t> dp = (gptr<uint8_t>)__shfl((unsigned long long)vdst, sl, kWave);
-      const uint32_t sn = uint32_t(__shfl(int(vlen), sl, kWave));
-      if (!sv) continue;
-      for (uint32_t i = 16 * (lane & 7u); i < sn; i += 128) copy_chunks(dp + i, sp + i, sn - i < 16 ? sn - i : 16u);
-    }
-    for (uint64_t m = __ballot(ok && vlen > 512); m; m &= m - 1) {
-      const int src_lane = __builtin_ctzll(m);
-      const gptr<const uint8_t> sp = (gptr<const uint8_t>)__shfl((unsigned long long)vsrc, src_lane, kWave);
-      const gptr<uint8_t> dp = (gptr<uint8_t>)__shfl((unsigned long long)vdst, src_lane, kWave);
-      const uint32_t sn = uint32_t(__shfl(int(vlen), src_lane, kWave));
-      for (uint32_t i = 16 * lane; i < sn; i += 16 * kWave) copy_chunks(dp + i, sp + i, sn - i < 16 ? sn - i : 16u);
-    }
+    result::copy_values(ok, vlen, vsrc, vdst);
   }
 }
 
 // ---- host side -----------------------------------------------------------------
-inline bool source_ok(const pbl_decode_out* d) {
-  return d->blk_status && d->blk_kv_base && d->blk_key_base && d->blk_val_base && d->key_off && d->val_off &&
-         d->key_bytes && d->val_bytes && d->trailer && !d->tiering_span_id == !d->tiering_attr;
-}
 // Argument checks shared by the device and the host entry points.
 inline bool args_ok(const pbl_merge_runs* in, const pbl_merge_out* out, bool size_only) {
   if (!in || !out || !in->runs) return false;
   if (in->n_runs == 0 || in->n_runs > kMaxRuns || in->comparer > PBL_CMP_CRDB) return false;
   for (uint32_t r = 0; r < in->n_runs; r++)
-    if (!source_ok(&in->runs[r])) return false;
-  const pbl_decode_out& o = out->result;
-  if (!o.blk_kv_base || !o.blk_key_base || !o.blk_val_base || !o.blk_status || !o.totals) return false;
-  if (size_only) return true;
-  if (!o.tiering_span_id != !o.tiering_attr) return false;
-  const bool any = o.kv_cap || o.key_cap || o.val_cap;  // (all zero: sizes are all that can come out)
-  if (any && (!o.trailer || !o.key_off || !o.val_off || !o.key_bytes || !o.val_bytes)) return false;
-  return true;
+    if (!result::source_ok(&in->runs[r])) return false;
+  return result::result_ok(out->result, size_only);
 }
 inline bool ws_ok(const void* ws, uint64_t bytes, uint32_t nb, uint64_t n_kv) {
-  return ws && !(reinterpret_cast<uintptr_t>(ws) & 15) && bytes >= layout(nb, n_kv).size;
+  return result::ws_aligned(ws) && bytes >= layout(nb, n_kv).size;
 }
 
 inline int launch(const pbl_merge_runs* in, pbl_merge_out* out, void* ws, uint64_t ws_bytes, bool size_only, bool sized,

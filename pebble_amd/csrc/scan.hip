@@ -14,20 +14,25 @@
 //       kv_hi) in global KV index space; the visible prefix at both ends (a
 //       tile prefix plus a partial tile) gives the query's sizes
 //   scan_sum_kernel / scan_bases_kernel  the exclusive scan over queries
-//       (chunks of 256: chunk sums, then each chunk adds the chunks before it):
-//       the result's bases, statuses, totals, the capacity check
+//       (result_core.hip.h's chunk_sums / bases, with the tiles per query as a
+//       fourth component): the result's bases, statuses, totals, the capacity
+//       check
 //   scan_emit_kernel  work item = (query, source tile), one wave each, a
 //       persistent grid striding over items whose number only the device knows;
 //       an item finds its query by binary search in the scanned tiles-per-query
 //       array.  Per-KV arrays lane per KV (output rank by ballot / popcount),
-//       keys lane per KV in 16-B chunks, values of at most 512 B 8 lanes per
-//       KV and longer ones by the whole wave, as tf_scatter_kernel copies them.
+//       keys lane per KV in 16-B chunks, values by result_core.hip.h's
+//       copy_values.
+//
+// The tile scan, every query's last offset and the per-KV arrays are
+// result_core.hip.h's too.
 //
 // bounds_one<R> is the whole bounds search; the kernel instantiates it with
 // GlobalReader and pbl_scan_batch_host with cmp::HostReader.
 #include <algorithm>
 #include <vector>
 
+#include "result_core.hip.h"
 #include "seek_core.hip.h"
 
 namespace pbl {
@@ -38,6 +43,7 @@ constexpr uint64_t kHdr = 64;
 constexpr uint32_t kTileShift = 8, kTile = 1u << kTileShift;  // source KVs per tile
 constexpr int kScanTPB = 256;
 constexpr uint32_t kChunk = 256;      // queries per chunk of the scan over queries
+static_assert(kScanTPB == result::kTPB && kChunk == uint32_t(result::kTPB), "result_core.hip.h's workgroup");
 constexpr uint32_t kEmitGrid = 2048;  // workgroups of the persistent emit grid, at most
 constexpr uint64_t kMaxBytes = 0xffffffffull;  // a query's key / value bytes (u32 offsets)
 // header words (u32): magic, comparer, n_blocks, hide, overflow (per call); u64
@@ -163,6 +169,8 @@ struct Ws {
     n_chunks = L.n_chunks;
   }
   __device__ gptr<uint64_t> q(int a) const { return q64 + uint64_t(a) * qs; }
+  // the four scanned components: kQKv, kQKey, kQVal, kQTiles
+  __device__ result::Sizes sizes() const { return result::Sizes{q(kQKv), csum, qst, qs, n_chunks}; }
   __device__ uint64_t prepared_kv() const { return *(gptr<const uint64_t>)(hdr + 6); }
 };
 
@@ -173,17 +181,8 @@ __device__ inline uint64_t source_total(const pbl_decode_out& D, uint32_t nb, ui
   return t < n_kv ? t : n_kv;
 }
 
-// The block that owns KV index kv (< blk_kv_base[nb]): the last b with
-// blk_kv_base[b] <= kv (blocks that own no KV index are stepped over).
-__device__ inline uint32_t block_of(gptr<const uint64_t> base, uint32_t nb, uint64_t kv) {
-  uint32_t lo = 0, hi = nb;
-  while (lo < hi) {
-    const uint32_t m = lo + (hi - lo) / 2;
-    if (base[m] <= kv) lo = m + 1;
-    else hi = m;
-  }
-  return lo ? lo - 1 : 0;
-}
+using result::block_of;
+using result::block_sum64;
 
 // One source KV as the scan sees it.
 struct Kv {
@@ -203,30 +202,6 @@ __device__ __forceinline__ Kv kv_view(const pbl_decode_out& D, bool hide, uint64
   r.ksrc = to_glb(D.blk_key_base)[b] + k0;
   r.vsrc = to_glb(D.blk_val_base)[b] + v0;
   return r;
-}
-
-// Sum of v over the workgroup (every thread gets it).  `lds`: 4 words.
-__device__ inline uint64_t block_sum64(uint64_t v, uint64_t* lds) {
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane_id() == 0) lds[wave_id()] = v;
-  __syncthreads();
-  return lds[0] + lds[1] + lds[2] + lds[3];
-}
-// Exclusive scan of v over the workgroup; *total = the sum.  `lds`: 4 words.
-__device__ inline uint64_t block_excl_scan64(uint64_t v, uint64_t* lds, uint64_t* total) {
-  const uint64_t inc = wave_incl_scan(v);
-  __syncthreads();
-  if (lane_id() == kWave - 1) lds[wave_id()] = inc;
-  __syncthreads();
-  uint64_t before = 0, t = 0;
-  for (int w = 0; w < kScanTPB / kWave; w++) {
-    const uint64_t s = lds[w];
-    if (w < wave_id()) before += s;
-    t += s;
-  }
-  *total = t;
-  return before + inc - v;
 }
 
 // Per tile: its visible KVs, key bytes and value bytes (scanned in place by
@@ -257,18 +232,7 @@ __global__ __launch_bounds__(kScanTPB) void scan_tile_kernel(ScanArgs A) {
 __global__ __launch_bounds__(kScanTPB) void scan_tile_scan_kernel(ScanArgs A) {
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, 0, A.n_blocks, A.n_kv);
-  uint64_t carry[3] = {0, 0, 0};
-  for (uint64_t t0 = 0; t0 < W.nt; t0 += kScanTPB) {
-    const uint64_t t = t0 + threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const uint64_t v = t < W.nt ? W.pfx[c][t] : 0;
-      uint64_t tot;
-      const uint64_t ex = block_excl_scan64(v, lds, &tot);
-      if (t < W.nt) W.pfx[c][t] = carry[c] + ex;
-      carry[c] += tot;
-    }
-  }
+  result::tile_scan_inplace(W.pfx, W.nt, lds);
   if (threadIdx.x == 0) {
     // a batch that holds more KVs than the workspace was sized for is not
     // described by it: no header, and every query reports it
@@ -397,12 +361,7 @@ __global__ __launch_bounds__(kScanTPB) void scan_bounds_kernel(ScanArgs A) {
 __global__ __launch_bounds__(kScanTPB) void scan_sum_kernel(ScanArgs A) {
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, A.q.n, A.n_blocks, A.n_kv);
-  const uint64_t i = uint64_t(blockIdx.x) * kChunk + threadIdx.x;
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    const uint64_t s = block_sum64(i < A.q.n ? W.q(kQKv + c)[i] : 0, lds);
-    if (threadIdx.x == 0) W.csum[uint64_t(c) * W.n_chunks + blockIdx.x] = s;
-  }
+  result::chunk_sums<4>(W.sizes(), A.q.n, lds);
 }
 
 // The result's bases, statuses and totals; the tiles-per-query scan; the
@@ -410,50 +369,21 @@ __global__ __launch_bounds__(kScanTPB) void scan_sum_kernel(ScanArgs A) {
 __global__ __launch_bounds__(kScanTPB) void scan_bases_kernel(ScanArgs A) {
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, A.q.n, A.n_blocks, A.n_kv);
-  const pbl_decode_out& O = A.out.result;
   const uint32_t n = A.q.n;
   const uint64_t i = uint64_t(blockIdx.x) * kChunk + threadIdx.x;
   uint64_t ex[4], end[4];
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    uint64_t before = 0;
-    for (uint32_t ch = threadIdx.x; ch < blockIdx.x; ch += kScanTPB) before += W.csum[uint64_t(c) * W.n_chunks + ch];
-    before = block_sum64(before, lds);
-    uint64_t tot;
-    ex[c] = before + block_excl_scan64(i < n ? W.q(kQKv + c)[i] : 0, lds, &tot);
-    end[c] = before + tot;
-  }
+  bool over;
+  const bool last = result::bases<4>(W.sizes(), A.out.result, n, A.size_only != 0, lds, ex, end, &over);
   if (i < n) {
-    to_glb(O.blk_kv_base)[i] = ex[0];
-    to_glb(O.blk_key_base)[i] = ex[1];
-    to_glb(O.blk_val_base)[i] = ex[2];
-    if (O.blk_rst_base) to_glb(O.blk_rst_base)[i] = 0;
     W.q(kQTBase)[i] = ex[3];
-    const uint32_t st = W.qst[i];
-    to_glb(O.blk_status)[i] = st;
-    if (st != PBL_OK) {
-      g_atomic_or(&O.totals->status_mask, 1u << st);
-      g_atomic_add(&O.totals->n_bad_blocks, 1u);
-    }
     if (A.out.range) {
       to_glb(A.out.range)[2 * i] = W.q(kQLo)[i];
       to_glb(A.out.range)[2 * i + 1] = W.q(kQHi)[i];
     }
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    to_glb(O.blk_kv_base)[n] = end[0];
-    to_glb(O.blk_key_base)[n] = end[1];
-    to_glb(O.blk_val_base)[n] = end[2];
-    if (O.blk_rst_base) to_glb(O.blk_rst_base)[n] = 0;
+  if (last) {
     W.q(kQTBase)[n] = end[3];
-    const gptr<pbl_totals> T = to_glb(O.totals);
-    T->n_kv = end[0];
-    T->key_bytes = end[1];
-    T->val_bytes = end[2];
-    T->n_restarts = 0;
-    const bool over = !A.size_only && (end[0] > O.kv_cap || end[1] > O.key_cap || end[2] > O.val_cap);
     W.hdr[kHOverflow] = over ? 1u : 0u;
-    if (over) g_atomic_or(&O.totals->status_mask, 1u << PBL_OVERFLOW);
   }
 }
 
@@ -470,12 +400,7 @@ scan_emit_kernel(ScanArgs A) {
   const uint32_t lane = lane_id();
   const bool hide = A.hide != 0;
   const gptr<const uint64_t> okvb = to_glb(O.blk_kv_base), okeyb = to_glb(O.blk_key_base), ovalb = to_glb(O.blk_val_base);
-  // every query's last offset (an empty query's only one)
-  for (uint64_t q = uint64_t(blockIdx.x) * kScanTPB + threadIdx.x; q < n; q += uint64_t(gridDim.x) * kScanTPB) {
-    const uint64_t at = okvb[q + 1] + q;
-    to_glb(O.key_off)[at] = uint32_t(okeyb[q + 1] - okeyb[q]);
-    to_glb(O.val_off)[at] = uint32_t(ovalb[q + 1] - ovalb[q]);
-  }
+  result::last_offsets(O, n, ~0ull);  // (an empty query's only offset)
   const gptr<const uint64_t> tbase = W.q(kQTBase), base = to_glb(I.blk_kv_base);
   const uint64_t n_items = tbase[n];
   const uint32_t wpb = kScanTPB / kWave;
@@ -525,42 +450,13 @@ scan_emit_kernel(ScanArgs A) {
       const uint32_t ko = kcur + kx - v.klen, vo = vcur + vx - v.vlen;
       if (vis) {
         const uint64_t k = okv + jo + rank;
-        to_glb(O.trailer)[k] = to_glb(I.trailer)[kv];
-        if (O.kv_flags) to_glb(O.kv_flags)[k] = I.kv_flags ? to_glb(I.kv_flags)[kv] : uint8_t(0);
-        if (O.entry_off && I.entry_off) to_glb(O.entry_off)[k] = to_glb(I.entry_off)[kv];
-        if (O.tiering_span_id && I.tiering_span_id) {  // KVMeta travels with its KV
-          to_glb(O.tiering_span_id)[k] = to_glb(I.tiering_span_id)[kv];
-          to_glb(O.tiering_attr)[k] = to_glb(I.tiering_attr)[kv];
-        }
+        result::copy_kv_arrays(O, k, I, kv, 0xff, false);
         if (A.out.src_kv) to_glb(A.out.src_kv)[k] = kv;
         to_glb(O.key_off)[k + q] = ko;
         to_glb(O.val_off)[k + q] = vo;
         copy_chunks(to_glb(O.key_bytes) + okb + ko, to_glb(I.key_bytes) + v.ksrc, v.klen);
       }
-      // values of at most 512 B: 8 lanes per KV (lane c of a group copies the
-      // value's 16-B chunks c, c + 8, ...); longer ones by the whole wave
-      // (tf_scatter_kernel's two forms and its threshold)
-#pragma unroll 1
-      for (uint32_t u = 0; u < kWave / 8; u++) {
-        const int sl = int(8 * u + (lane >> 3));
-        const bool sv = __shfl(int(vis && v.vlen <= 512), sl, kWave) != 0;
-        const uint64_t so = __shfl((unsigned long long)v.vsrc, sl, kWave);
-        const uint32_t sn = uint32_t(__shfl(int(v.vlen), sl, kWave));
-        const uint32_t dofs = uint32_t(__shfl(int(vo), sl, kWave));
-        if (!sv) continue;
-        const gptr<const uint8_t> sp = to_glb(I.val_bytes) + so;
-        const gptr<uint8_t> dp = to_glb(O.val_bytes) + ovb + dofs;
-        for (uint32_t i = 16 * (lane & 7u); i < sn; i += 128) copy_chunks(dp + i, sp + i, sn - i < 16 ? sn - i : 16u);
-      }
-      for (uint64_t m = __ballot(vis && v.vlen > 512); m; m &= m - 1) {
-        const int src_lane = __builtin_ctzll(m);
-        const uint64_t so = __shfl((unsigned long long)v.vsrc, src_lane, kWave);
-        const uint32_t sn = uint32_t(__shfl(int(v.vlen), src_lane, kWave));
-        const uint32_t dofs = uint32_t(__shfl(int(vo), src_lane, kWave));
-        const gptr<const uint8_t> sp = to_glb(I.val_bytes) + so;
-        const gptr<uint8_t> dp = to_glb(O.val_bytes) + ovb + dofs;
-        for (uint32_t i = 16 * lane; i < sn; i += 16 * kWave) copy_chunks(dp + i, sp + i, sn - i < 16 ? sn - i : 16u);
-      }
+      result::copy_values(vis, v.vlen, to_glb((const uint8_t*)I.val_bytes) + v.vsrc, to_glb(O.val_bytes) + (ovb + vo));
       jo += __builtin_popcountll(vm);
       kcur += uint32_t(__shfl(int(kx), kWave - 1, kWave));
       vcur += uint32_t(__shfl(int(vx), kWave - 1, kWave));
@@ -569,26 +465,16 @@ scan_emit_kernel(ScanArgs A) {
 }
 
 // ---- host side -----------------------------------------------------------------
-inline bool source_ok(const pbl_decode_out* d) {
-  return d && d->blk_status && d->blk_kv_base && d->blk_key_base && d->blk_val_base && d->key_off && d->val_off &&
-         d->key_bytes && d->val_bytes && d->trailer && !d->tiering_span_id == !d->tiering_attr;
-}
 // Argument checks shared by the device and the host entry points.
 inline bool args_ok(const pbl_decode_out* d, const pbl_scan_queries* q, const pbl_scan_out* out, bool size_only) {
-  if (!source_ok(d) || !q || !out) return false;
+  if (!result::source_ok(d) || !q || !out) return false;
   if (q->comparer > PBL_CMP_CRDB) return false;
   if (!q->lower_off || !q->upper_off || (q->n && (!q->lower_bytes || !q->upper_bytes))) return false;
   if (q->hide_obsolete_points && !d->kv_flags) return false;
-  const pbl_decode_out& o = out->result;
-  if (!o.blk_kv_base || !o.blk_key_base || !o.blk_val_base || !o.blk_status || !o.totals) return false;
-  if (size_only) return true;
-  if (!o.tiering_span_id != !o.tiering_attr) return false;
-  const bool any = o.kv_cap || o.key_cap || o.val_cap;  // (all zero: sizes are all that can come out)
-  if (any && (!o.trailer || !o.key_off || !o.val_off || !o.key_bytes || !o.val_bytes)) return false;
-  return true;
+  return result::result_ok(out->result, size_only);
 }
 inline bool ws_ok(const void* ws, uint64_t bytes, uint32_t nq, uint32_t nb, uint64_t n_kv) {
-  return ws && !(reinterpret_cast<uintptr_t>(ws) & 15) && bytes >= layout(nq, nb, n_kv).size;
+  return result::ws_aligned(ws) && bytes >= layout(nq, nb, n_kv).size;
 }
 
 inline int launch(const pbl_decode_out* d, uint32_t nb, uint64_t n_kv, const pbl_scan_queries* q, pbl_scan_out* out, void* ws,
@@ -637,7 +523,7 @@ uint64_t pbl_scan_workspace_bytes(uint32_t n_queries, uint32_t n_blocks, uint64_
 int pbl_scan_prepare(const pbl_decode_out* decoded, uint32_t n_blocks, uint64_t n_kv, uint32_t comparer,
                      uint32_t hide_obsolete_points, void* workspace, uint64_t workspace_bytes, void* stream) {
   namespace S = pbl::scan;
-  if (!S::source_ok(decoded) || comparer > PBL_CMP_CRDB || (hide_obsolete_points && !decoded->kv_flags) ||
+  if (!pbl::result::source_ok(decoded) || comparer > PBL_CMP_CRDB || (hide_obsolete_points && !decoded->kv_flags) ||
       !S::ws_ok(workspace, workspace_bytes, 0, n_blocks, n_kv))
     return PBL_INVALID_ARG;
   const S::Layout L = S::layout(0, n_blocks, n_kv);

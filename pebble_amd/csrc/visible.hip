@@ -28,18 +28,20 @@
 //   visible_persize_kernel  lane per block: status, and sizes as differences of
 //       the prefixes at the block's two ends
 //   visible_sum_kernel / visible_bases_kernel  the exclusive scan over result
-//       blocks (chunks of 256, as merge.hip's): bases, statuses, totals, capacity
+//       blocks (result_core.hip.h's chunk_sums / bases): bases, statuses,
+//       totals, capacity
 //   visible_heads_kernel  wave per 64 source KVs: a KV that is a result writes
-//       its per-KV arrays, offsets and key (scan_emit_kernel's form)
+//       its per-KV arrays (result_core.hip.h's copy_kv_arrays, flags masked to
+//       the handle bits), offsets and key; every block's last offset
 //   visible_values_kernel  wave per 64 source KVs: every contributing KV copies
 //       its value to X[r] + X[r+1] - P[i] (X: the result's value offsets, P: the
 //       inclusive value prefix), so a chain's oldest operand comes first and no
 //       lane looks for its chain's end; n_src from the heads' contributor counts.
-//       8 lanes per value of at most 512 B, the whole wave for longer ones.
+//       The copy itself is result_core.hip.h's copy_values.
 //
 // The cross-tile steps use the two-launch chunk form of the scans over blocks
-// rather than merge.hip's one workgroup over all tiles (measured first in that
-// form: 76 + 182 us of a 500 us size call at 17 K tiles).  The maps do not
+// rather than result_core.hip.h's one workgroup over all tiles (measured first in
+// that form: 76 + 182 us of a 500 us size call at 17 K tiles).  The maps do not
 // commute, so where the sums add the earlier chunks' totals in any order, the
 // state kernel scans them in order, 256 chunks (16.7 M KVs) per step.
 //
@@ -52,6 +54,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "result_core.hip.h"
 #include "seek_core.hip.h"
 
 namespace pbl {
@@ -61,6 +64,7 @@ constexpr uint64_t kHdr = 64;
 constexpr uint32_t kTileShift = 8, kTile = 1u << kTileShift;  // source KVs per tile
 constexpr int kTPB = 256;
 constexpr uint32_t kChunk = 256;  // result blocks per chunk of the scan over blocks
+static_assert(kTPB == result::kTPB && kChunk == uint32_t(result::kTPB), "result_core.hip.h's workgroup");
 constexpr uint32_t kGrid = 2048;  // workgroups of a grid-striding kernel, at most
 constexpr uint64_t kMaxBytes = 0xffffffffull;
 constexpr uint64_t kMaxKvs = 0xffffffffull;
@@ -176,6 +180,7 @@ struct Ws {
     n_chunks = L.n_chunks;
   }
   __device__ gptr<uint64_t> q(int c) const { return q64 + uint64_t(c) * qs; }   // per-block KVs, key bytes, value bytes
+  __device__ result::Sizes sizes() const { return result::Sizes{q64, csum, qst, qs, n_chunks}; }
   __device__ gptr<uint64_t> ts(int c) const { return tsum + uint64_t(c) * nt; }  // per-tile sums
   // per-KV exclusive prefixes (n_kv + 1 entries each): 0 heads, 1 contributors, 2 key bytes, 3 value bytes
   __device__ gptr<uint64_t> p(int c) const { return pre + uint64_t(c) * ps; }
@@ -186,41 +191,11 @@ enum { kPH = 0, kPC = 1, kPK = 2, kPV = 3 };
 __device__ inline uint64_t held(const Args& A) { return A.n_blocks ? to_glb(A.in.blk_kv_base)[A.n_blocks] : 0; }
 __device__ inline bool described(const Args& A) { return held(A) <= A.n_kv; }
 
-// The block that owns KV index kv: the last b with base[b] <= kv.
-__device__ inline uint32_t block_of(gptr<const uint64_t> base, uint32_t nb, uint64_t kv) {
-  uint32_t lo = 0, hi = nb;
-  while (lo < hi) {
-    const uint32_t m = lo + (hi - lo) / 2;
-    if (base[m] <= kv) lo = m + 1;
-    else hi = m;
-  }
-  return lo ? lo - 1 : 0;
-}
+using result::block_excl_scan64;
+using result::block_of;
+using result::block_sum64;
 
-// Sum of v over the workgroup (every thread gets it).  `lds`: 4 words.
-__device__ inline uint64_t block_sum64(uint64_t v, uint64_t* lds) {
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane_id() == 0) lds[wave_id()] = v;
-  __syncthreads();
-  return lds[0] + lds[1] + lds[2] + lds[3];
-}
-// Exclusive scan of v over the workgroup; *total = the sum.  `lds`: 4 words.
-__device__ inline uint64_t block_excl_scan64(uint64_t v, uint64_t* lds, uint64_t* total) {
-  const uint64_t inc = wave_incl_scan(v);
-  __syncthreads();
-  if (lane_id() == kWave - 1) lds[wave_id()] = inc;
-  __syncthreads();
-  uint64_t before = 0, t = 0;
-  for (int w = 0; w < kTPB / kWave; w++) {
-    const uint64_t s = lds[w];
-    if (w < wave_id()) before += s;
-    t += s;
-  }
-  *total = t;
-  return before + inc - v;
-}
-// The same for maps under map_then: the composition of the maps of the threads
+// block_excl_scan64 for maps under map_then: the composition of the maps of the threads
 // before this one (the identity for thread 0); *total = all 256.  `lds`: 4 words.
 __device__ inline uint32_t block_excl_scan_map(uint32_t m, uint32_t* lds, uint32_t* total) {
   const int l = lane_id();
@@ -464,12 +439,7 @@ __global__ __launch_bounds__(kTPB) void visible_persize_kernel(Args A) {
 __global__ __launch_bounds__(kTPB) void visible_sum_kernel(Args A) {
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, A.n_blocks, A.n_kv);
-  const uint64_t i = uint64_t(blockIdx.x) * kChunk + threadIdx.x;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const uint64_t s = block_sum64(i < A.n_blocks ? W.q(c)[i] : 0, lds);
-    if (threadIdx.x == 0) W.csum[uint64_t(c) * W.n_chunks + blockIdx.x] = s;
-  }
+  result::chunk_sums<3>(W.sizes(), A.n_blocks, lds);
 }
 
 // The result's bases, statuses and totals; the capacity check (the last chunk).
@@ -477,45 +447,10 @@ __global__ __launch_bounds__(kTPB) void visible_sum_kernel(Args A) {
 __global__ __launch_bounds__(kTPB) void visible_bases_kernel(Args A) {
   __shared__ uint64_t lds[4];
   const Ws W(A.ws, A.n_blocks, A.n_kv);
-  const pbl_decode_out& O = A.out.result;
-  const uint32_t n = A.n_blocks;
-  const uint64_t i = uint64_t(blockIdx.x) * kChunk + threadIdx.x;
   uint64_t ex[3], end[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    uint64_t before = 0;
-    for (uint32_t ch = threadIdx.x; ch < blockIdx.x; ch += kTPB) before += W.csum[uint64_t(c) * W.n_chunks + ch];
-    before = block_sum64(before, lds);
-    uint64_t tot;
-    ex[c] = before + block_excl_scan64(i < n ? W.q(c)[i] : 0, lds, &tot);
-    end[c] = before + tot;
-  }
-  if (i < n) {
-    to_glb(O.blk_kv_base)[i] = ex[0];
-    to_glb(O.blk_key_base)[i] = ex[1];
-    to_glb(O.blk_val_base)[i] = ex[2];
-    if (O.blk_rst_base) to_glb(O.blk_rst_base)[i] = 0;
-    const uint32_t st = W.qst[i];
-    to_glb(O.blk_status)[i] = st;
-    if (st != PBL_OK) {
-      g_atomic_or(&O.totals->status_mask, 1u << st);
-      g_atomic_add(&O.totals->n_bad_blocks, 1u);
-    }
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    to_glb(O.blk_kv_base)[n] = end[0];
-    to_glb(O.blk_key_base)[n] = end[1];
-    to_glb(O.blk_val_base)[n] = end[2];
-    if (O.blk_rst_base) to_glb(O.blk_rst_base)[n] = 0;
-    const gptr<pbl_totals> T = to_glb(O.totals);
-    T->n_kv = end[0];
-    T->key_bytes = end[1];
-    T->val_bytes = end[2];
-    T->n_restarts = 0;
-    const bool over = !A.size_only && (end[0] > O.kv_cap || end[1] > O.key_cap || end[2] > O.val_cap);
+  bool over;
+  if (result::bases<3>(W.sizes(), A.out.result, A.n_blocks, A.size_only != 0, lds, ex, end, &over))
     W.hdr[kHSkip] = (over || !described(A)) ? 1u : 0u;
-    if (over) g_atomic_or(&O.totals->status_mask, 1u << PBL_OVERFLOW);
-  }
 }
 
 // A source KV and the place of what it contributes to.
@@ -554,7 +489,7 @@ __device__ inline Place place_of(const Args& A, const Ws& W, uint64_t i) {
 }
 
 #ifndef PBL_VISIBLE_EMIT_WAVES
-#define PBL_VISIBLE_EMIT_WAVES 5  // as scan_emit_kernel: the same copy loops
+#define PBL_VISIBLE_EMIT_WAVES 5  // as every caller of result::copy_values
 #endif
 // Every result KV's arrays, offsets and key; every block's last offset.
 __global__ void __launch_bounds__(kTPB) __attribute__((amdgpu_waves_per_eu(PBL_VISIBLE_EMIT_WAVES)))
@@ -563,15 +498,8 @@ visible_heads_kernel(Args A) {
   if (W.hdr[kHSkip] != 0) return;  // sizes only
   const pbl_decode_out& O = A.out.result;
   const pbl_decode_out& I = A.in;
-  const uint32_t nb = A.n_blocks;
-  const gptr<const uint64_t> okvb = to_glb((const uint64_t*)O.blk_kv_base), okeyb = to_glb((const uint64_t*)O.blk_key_base),
-                             ovalb = to_glb((const uint64_t*)O.blk_val_base);
-  for (uint64_t q = uint64_t(blockIdx.x) * kTPB + threadIdx.x; q < nb; q += uint64_t(gridDim.x) * kTPB) {
-    const uint64_t at = okvb[q + 1] + q;
-    if (okvb[q + 1] > O.kv_cap) continue;
-    to_glb(O.key_off)[at] = uint32_t(okeyb[q + 1] - okeyb[q]);
-    to_glb(O.val_off)[at] = uint32_t(ovalb[q + 1] - ovalb[q]);
-  }
+  const gptr<const uint64_t> okeyb = to_glb((const uint64_t*)O.blk_key_base);
+  result::last_offsets(O, A.n_blocks, O.kv_cap);
   const uint64_t n = held(A);
   const uint64_t n_items = (n + kWave - 1) / kWave;
   const uint32_t wpb = kTPB / kWave;
@@ -587,13 +515,7 @@ visible_heads_kernel(Args A) {
     const uint64_t ko = W.p(kPK)[i] - W.p(kPK)[P.kv0], vo = W.p(kPV)[i] - W.p(kPV)[P.kv0];
     if (ko + klen > P.ksize || vo > P.vsize) continue;
     const uint64_t p = P.p;
-    to_glb(O.trailer)[p] = to_glb(I.trailer)[i];
-    if (O.kv_flags) to_glb(O.kv_flags)[p] = I.kv_flags ? uint8_t(to_glb(I.kv_flags)[i] & kHandleBits) : uint8_t(0);
-    if (O.entry_off) to_glb(O.entry_off)[p] = I.entry_off ? to_glb(I.entry_off)[i] : 0u;
-    if (O.tiering_span_id) {  // KVMeta travels with its KV
-      to_glb(O.tiering_span_id)[p] = I.tiering_span_id ? to_glb(I.tiering_span_id)[i] : 0ull;
-      to_glb(O.tiering_attr)[p] = I.tiering_attr ? to_glb(I.tiering_attr)[i] : 0ull;
-    }
+    result::copy_kv_arrays(O, p, I, i, uint8_t(kHandleBits), true);
     if (A.out.src_kv) to_glb(A.out.src_kv)[p] = i;
     to_glb(O.key_off)[p + P.q] = uint32_t(ko);
     to_glb(O.val_off)[p + P.q] = uint32_t(vo);
@@ -654,48 +576,19 @@ visible_values_kernel(Args A) {
         }
       }
     }
-    // values of at most 512 B: 8 lanes per KV (lane c of a group copies the
-    // value's 16-B chunks c, c + 8, ...); longer ones by the whole wave
-    // (scan_emit_kernel's two forms and its threshold)
-#pragma unroll 1
-    for (uint32_t u = 0; u < kWave / 8; u++) {
-      const int sl = int(8 * u + (lane >> 3));
-      const bool sv = __shfl(int(ok && vlen <= 512), sl, kWave) != 0;
-      const gptr<const uint8_t> sp = (gptr<const uint8_t>)__shfl((unsigned long long)vsrc, sl, kWave);
-      const gptr<uint8_t> dp = (gptr<uint8_t>)__shfl((unsigned long long)vdst, sl, kWave);
-      const uint32_t sn = uint32_t(__shfl(int(vlen), sl, kWave));
-      if (!sv) continue;
-      for (uint32_t c = 16 * (lane & 7u); c < sn; c += 128) copy_chunks(dp + c, sp + c, sn - c < 16 ? sn - c : 16u);
-    }
-    for (uint64_t m = __ballot(ok && vlen > 512); m; m &= m - 1) {
-      const int src_lane = __builtin_ctzll(m);
-      const gptr<const uint8_t> sp = (gptr<const uint8_t>)__shfl((unsigned long long)vsrc, src_lane, kWave);
-      const gptr<uint8_t> dp = (gptr<uint8_t>)__shfl((unsigned long long)vdst, src_lane, kWave);
-      const uint32_t sn = uint32_t(__shfl(int(vlen), src_lane, kWave));
-      for (uint32_t c = 16 * lane; c < sn; c += 16 * kWave) copy_chunks(dp + c, sp + c, sn - c < 16 ? sn - c : 16u);
-    }
+    result::copy_values(ok, vlen, vsrc, vdst);
   }
 }
 
 // ---- host side -----------------------------------------------------------------
-inline bool source_ok(const pbl_decode_out* d) {
-  return d->blk_status && d->blk_kv_base && d->blk_key_base && d->blk_val_base && d->key_off && d->val_off &&
-         d->key_bytes && d->val_bytes && d->trailer && !d->tiering_span_id == !d->tiering_attr;
-}
 // Argument checks shared by the device and the host entry points.
 inline bool args_ok(const pbl_visible_in* in, const pbl_visible_out* out, uint32_t flags, uint32_t allowed, bool size_only) {
   if (!in || !out || (flags & ~allowed)) return false;
-  if (in->comparer > PBL_CMP_CRDB || !source_ok(&in->batch)) return false;
-  const pbl_decode_out& o = out->result;
-  if (!o.blk_kv_base || !o.blk_key_base || !o.blk_val_base || !o.blk_status || !o.totals) return false;
-  if (size_only) return true;
-  if (!o.tiering_span_id != !o.tiering_attr) return false;
-  const bool any = o.kv_cap || o.key_cap || o.val_cap;  // (all zero: sizes are all that can come out)
-  if (any && (!o.trailer || !o.key_off || !o.val_off || !o.key_bytes || !o.val_bytes)) return false;
-  return true;
+  if (in->comparer > PBL_CMP_CRDB || !result::source_ok(&in->batch)) return false;
+  return result::result_ok(out->result, size_only);
 }
 inline bool ws_ok(const void* ws, uint64_t bytes, uint32_t nb, uint64_t n_kv) {
-  return ws && !(reinterpret_cast<uintptr_t>(ws) & 15) && bytes >= layout(nb, n_kv).size;
+  return result::ws_aligned(ws) && bytes >= layout(nb, n_kv).size;
 }
 
 inline int launch(const pbl_visible_in* in, pbl_visible_out* out, void* ws, uint64_t ws_bytes, uint32_t flags,
