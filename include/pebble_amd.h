@@ -1147,6 +1147,135 @@ int pbl_visible_batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint3
  * field offsets (the other layout lists are unchanged). */
 size_t pbl_visible_struct_layout(uint64_t* out, size_t cap);
 
+/* ---- range deletions in the read path, on the device ----
+ * mergingIter skips a point k#s when some range tombstone [start, end)#t has
+ * cmp(start, k) <= 0 && cmp(k, end) < 0, t visible at the snapshot and t > s
+ * (isNextEntryDeleted, merging_iter.go:605; keyspan.Span.VisibleAt / CoversAt,
+ * internal/keyspan/span.go:336, :396).  The reference applies t > s level by
+ * level; under the LSM invariant (a deeper level holds no sequence number newer
+ * than a shallower one) that equals the pure sequence-number rule, which is
+ * what is built here: a KV is range-deleted iff
+ *   max{t : tombstone visible at the snapshot and covering k} > s.
+ * A point with s == t survives.  A tombstone is visible as a point is (rule 1
+ * of the view above: t < snapshot, PBL_SEQNUM_MAX sees everything).
+ *
+ * A RUN is one table's range-deletion fragments as a decoded batch with ONE
+ * block: what pbl_decode_batch (flags 0) produces from a row-format range-del
+ * block (restart interval 1, no prefix sharing, rowblk_fragment_iter.go:116-139).
+ * Per KV the key is the start user key, the trailer seq << 8 | 15
+ * (InternalKeyKindRangeDelete), the value the end user key.  A valid run is
+ * FRAGMENTED, as every sstable's is: KVs sorted by (start ascending under the
+ * comparer, trailer descending); every fragment has start <= end (an empty one,
+ * start == end, covers nothing; real tables hold such); two
+ * consecutive fragments either have equal start and equal end, or
+ * end_i <= start_{i+1}.  key_bytes and val_bytes must be readable 16 B past
+ * their end, as for every source.
+ *
+ * pbl_rangedel_set flattens up to PBL_RANGEDEL_MAX_RUNS runs into the SET: a
+ * decoded batch with one block whose KVs are the distinct boundary keys (every
+ * start and every end of every run) ascending under the comparer.  Among
+ * boundaries that compare equal the bytes are those of the first in (run,
+ * fragment index, start before end) order.  Values are empty, kv_flags 0,
+ * entry_off 0, and KV i has trailer cover_i << 8 | 15, cover_i the largest
+ * visible t among the fragments of any run with start <= b_i < end, or 0 when
+ * there is none (t = 0 covers nothing; the last boundary always has cover 0).
+ * to_host(), the host iterator and the per-block seeks read the set unchanged.
+ * No size call: at most 2T KVs and the runs' summed key and value bytes come
+ * out (T = the runs' KVs), and a caller allocates those bounds; a smaller
+ * capacity writes the sizes, no bytes, and PBL_OVERFLOW in totals.status_mask.
+ * blk_status[0], the set being empty on any of them, in order of precedence:
+ * the first run block status that is not PBL_OK, in run order; a kind other
+ * than RANGEDEL, or PBL_KV_INVALID_KEY: PBL_UNSUPPORTED; a run that is not
+ * fragmented as defined above, or that holds another number of KVs than
+ * n_kv[r]: PBL_INVALID_ARG.  The workspace (DEVICE, 16-byte aligned,
+ * pbl_rangedel_workspace_bytes(T)) serves one call at a time.  Stream-ordered,
+ * no host synchronisation.
+ *
+ * pbl_rangedel_cover: for every KV of `batch` (n_blocks blocks, n_kv = its
+ * totals.n_kv as the host read it), cover_seq[kv] (DEVICE [n_kv]) = the cover
+ * of the last boundary <= the KV's user key, 0 before the first boundary.  An
+ * empty set, or one whose blk_status[0] is not PBL_OK, gives all zeros, and so
+ * does a KV of a block that is not PBL_OK.  The call is asynchronous like every
+ * device entry point, so it cannot return the set's status: that stays in
+ * set->blk_status[0] and set->totals->status_mask, which the caller of
+ * pbl_rangedel_set reads once with the sizes.  One launch, no workspace.
+ *
+ * pbl_visible_size_rd / pbl_visible_batch_rd / pbl_visible_batch_host_rd are the
+ * view above with rule 1 extended: a KV is visible iff trailer >> 8 < snapshot
+ * and not cover_seq[kv] > trailer >> 8 (cover_seq: [in->n_kv] entries, DEVICE or
+ * HOST as `in`; NULL = no range deletions, which is what the three entry points
+ * above pass).  A range-deleted KV is an invisible KV everywhere: it heads no
+ * group, is no operand and ends no MERGE chain.  Nothing else in the rules
+ * changes.  With PBL_VISIBLE_SIZED the roles are the size call's and cover_seq
+ * is not read again.
+ *
+ * The host forms take HOST arrays and use other algorithms, so that they and
+ * the device check each other: pbl_rangedel_set_host sorts all boundaries
+ * (std::stable_sort, unique) and takes a brute-force maximum over all
+ * fragments per boundary; pbl_rangedel_cover_host takes the RUNS, not the set,
+ * and brute-forces the maximum over every fragment per KV, so that it checks
+ * the set builder and the lookup together; *status (optional) receives the
+ * status the set would have.
+ *
+ * Levels.  The reference applies t > s level by level (isNextEntryDeleted): a
+ * visible covering tombstone of a SHALLOWER level (a newer memtable, a newer L0
+ * sublevel, a lower-numbered level) deletes a point whatever the two sequence
+ * numbers are; one of the point's own level needs t > s.  In an LSM whose
+ * sequence numbers are ordered by level the two forms agree; where a caller's
+ * inputs may not be (testdata/range_del holds such memtables), it passes
+ * levels: runs->level[r] for the tombstones, and to pbl_rangedel_cover_lv per
+ * KV the run (table) it came from (src_run, DEVICE u8 [n_kv], what
+ * pbl_merge_batch writes) and that run's level (run_level, HOST [16]).  The set
+ * then holds in entry_off[i] (required with levels) 1 + the shallowest level
+ * with a visible fragment covering b_i (0: none), and cover_seq[kv] is
+ * PBL_RANGEDEL_ALL, above every sequence number, where that level is shallower
+ * than the KV's, else the cover as above (a tombstone of a deeper level is
+ * still judged by its sequence number).  Without levels (NULL) entry_off is 0
+ * and the rule is the sequence-number one.  pbl_rangedel_cover is
+ * pbl_rangedel_cover_lv with NULLs.
+ *
+ * PBL_INVALID_ARG, before any device call: NULL runs / set / batch / cover_seq
+ * or a needed array, more than PBL_RANGEDEL_MAX_RUNS runs, runs->runs or
+ * runs->n_kv NULL with n_runs > 0, comparer > PBL_CMP_CRDB, 2^31 fragments or
+ * more, a workspace that is NULL, not 16-byte aligned or too short.
+ */
+#define PBL_RANGEDEL_MAX_RUNS 16
+#define PBL_KIND_RANGEDEL 15u /* InternalKeyKindRangeDelete (internal/base/internal.go:29-130) */
+#define PBL_RANGEDEL_ALL (1ull << 56) /* a cover above every sequence number: deleted by a shallower level */
+
+typedef struct pbl_rangedel_runs {
+  const pbl_decode_out* runs; /* HOST array [n_runs]; one block each; the arrays each names are DEVICE
+                                 (HOST for the host forms); capacities and workspace fields unused */
+  const uint64_t* n_kv;       /* HOST [n_runs]: each run's totals.n_kv as the host read it */
+  uint32_t n_runs, comparer /* PBL_CMP_* */;
+  uint64_t snapshot;
+  const uint8_t* level;       /* HOST [n_runs] or NULL: each run's level, smaller = shallower (see "Levels") */
+} pbl_rangedel_runs;
+
+uint64_t pbl_rangedel_workspace_bytes(uint64_t n_fragments);
+int pbl_rangedel_set(const pbl_rangedel_runs* runs, pbl_decode_out* set, void* workspace, uint64_t workspace_bytes,
+                     void* stream);
+int pbl_rangedel_set_host(const pbl_rangedel_runs* runs, pbl_decode_out* set);
+int pbl_rangedel_cover(const pbl_decode_out* set, const pbl_decode_out* batch, uint32_t n_blocks, uint64_t n_kv,
+                       uint32_t comparer, uint64_t* cover_seq, void* stream);
+int pbl_rangedel_cover_host(const pbl_rangedel_runs* runs, const pbl_decode_out* batch, uint32_t n_blocks,
+                            uint64_t* cover_seq, uint32_t* status);
+int pbl_rangedel_cover_lv(const pbl_decode_out* set, const pbl_decode_out* batch, uint32_t n_blocks, uint64_t n_kv,
+                          uint32_t comparer, const uint8_t* src_run, const uint8_t* run_level, uint64_t* cover_seq,
+                          void* stream);
+int pbl_rangedel_cover_host_lv(const pbl_rangedel_runs* runs, const pbl_decode_out* batch, uint32_t n_blocks,
+                               const uint8_t* src_run, const uint8_t* run_level, uint64_t* cover_seq,
+                               uint32_t* status);
+int pbl_visible_size_rd(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
+                        uint32_t flags, const uint64_t* cover_seq, void* stream);
+int pbl_visible_batch_rd(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
+                         uint32_t flags, const uint64_t* cover_seq, void* stream);
+int pbl_visible_batch_host_rd(const pbl_visible_in* in, pbl_visible_out* out, uint32_t flags,
+                              const uint64_t* cover_seq);
+/* sizeof(pbl_rangedel_runs), its 6 field offsets (the other layout lists are
+ * unchanged; ABI version 9 stands). */
+size_t pbl_rangedel_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@ C-ABI declared in include/pebble_amd.h.  This package is the host layer:
   pebble_amd.seek    batched SeekGE / SeekLT over a DecodedBatch, on the device
   pebble_amd.scan    batched bounded scans over a DecodedBatch, on the device
   pebble_amd.merge   batched k-way merge of sorted DecodedBatches, on the device
+  pebble_amd.visible the snapshot-visible view of a sorted DecodedBatch, and read()
+  pebble_amd.rangedel range deletions in that path: the flattened set and the per-KV cover
 """
 from . import _native  # noqa: F401
 

@@ -239,6 +239,18 @@ class VisibleOutC(ctypes.Structure):  # pbl_visible_out
     _fields_ = [("result", DecodeOutC), ("src_kv", _vp), ("n_src", _vp)]
 
 
+# range deletions in the read path (pbl_rangedel_set, pbl_rangedel_cover, the view's _rd entry points)
+PBL_RANGEDEL_MAX_RUNS = 16
+PBL_KIND_RANGEDEL = 15
+PBL_RANGEDEL_ALL = 1 << 56  # a cover above every sequence number
+
+
+class RangedelRunsC(ctypes.Structure):  # pbl_rangedel_runs
+    _fields_ = [("runs", ctypes.POINTER(DecodeOutC)), ("n_kv", ctypes.POINTER(ctypes.c_uint64)),
+                ("n_runs", ctypes.c_uint32), ("comparer", ctypes.c_uint32), ("snapshot", ctypes.c_uint64),
+                ("level", ctypes.POINTER(ctypes.c_uint8))]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -301,6 +313,25 @@ SIGNATURES = {
     "pbl_visible_batch_host": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC),
                                               ctypes.c_uint32]),
     "pbl_visible_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_rangedel_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "pbl_rangedel_set": (ctypes.c_int, [ctypes.POINTER(RangedelRunsC), ctypes.POINTER(DecodeOutC), _vp, ctypes.c_uint64,
+                                        _vp]),
+    "pbl_rangedel_set_host": (ctypes.c_int, [ctypes.POINTER(RangedelRunsC), ctypes.POINTER(DecodeOutC)]),
+    "pbl_rangedel_cover": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
+                                          ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
+    "pbl_rangedel_cover_host": (ctypes.c_int, [ctypes.POINTER(RangedelRunsC), ctypes.POINTER(DecodeOutC),
+                                               ctypes.c_uint32, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "pbl_rangedel_cover_lv": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
+                                             ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "pbl_rangedel_cover_host_lv": (ctypes.c_int, [ctypes.POINTER(RangedelRunsC), ctypes.POINTER(DecodeOutC),
+                                                  ctypes.c_uint32, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "pbl_visible_size_rd": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC), _vp,
+                                           ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
+    "pbl_visible_batch_rd": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC), _vp,
+                                            ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
+    "pbl_visible_batch_host_rd": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC),
+                                                 ctypes.c_uint32, _vp]),
+    "pbl_rangedel_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

@@ -16,7 +16,9 @@
 //   visible_classify_kernel<comparer>  tile of 256 source KVs per workgroup: a
 //       lane compares its KV with the successor (sortedness, and whether the
 //       successor starts a group), checks kind and flags, writes the KV's class
-//       and block; the tile's composed map
+//       and block; the tile's composed map.  Instantiated on "has cover": with
+//       the per-KV cover of rangedel.hip (the _rd entry points)
+//       a KV under a newer range tombstone is invisible too
 //   visible_chunk_map_kernel / visible_state_kernel  every tile's incoming
 //       state: the scan of the tile maps in the chunked two-launch form (chunks
 //       of 256 tiles; a chunk composes the maps of the chunks before it in order)
@@ -50,7 +52,7 @@
 // workspace, leads outside the arrays.
 //
 // pbl_visible_batch_host is the sequential state machine over the same
-// comparers, a different algorithm on purpose.
+// comparers, a different algorithm on purpose (batch_host<has cover>).
 #include <algorithm>
 #include <vector>
 
@@ -149,6 +151,7 @@ struct Args {
   uint64_t n_kv;  // the batch's KVs, as the workspace was sized
   uint64_t snapshot;
   uint8_t* ws;
+  const uint64_t* cover;  // [n_kv] per KV: the newest visible range tombstone over its key (rangedel.hip), or NULL
 };
 
 struct Ws {
@@ -227,7 +230,9 @@ __device__ inline seek::View<GR> in_view(const Args& A) {
   return seek::View<GR>(A.in, A.n_blocks, sq, nullptr, 0);
 }
 
-template <uint32_t kCmp>
+// kCover: the batch comes with a cover (the _rd entry points); a KV under a newer
+// range tombstone is invisible like one at or above the snapshot.
+template <uint32_t kCmp, bool kCover>
 __global__ __launch_bounds__(kTPB) void visible_classify_kernel(Args A) {
   __shared__ uint32_t lds[4];
   __shared__ uint32_t next_head[kTile];  // whether the KV after this thread's starts a group
@@ -254,6 +259,9 @@ __global__ __launch_bounds__(kTPB) void visible_classify_kernel(Args A) {
         uint32_t cls = kind_class(ti, &kind_ok);
         uint32_t badw = (kind_ok && !(f & PBL_KV_INVALID_KEY)) ? 0u : kBadKind;
         if (!is_visible(ti, A.snapshot)) cls = kNone;
+        if constexpr (kCover) {
+          if (to_glb(A.cover)[i] > (ti >> 8)) cls = kNone;
+        }
         code = cls | ((f & kHandleBits) ? kCodeHandle : 0u);
         first_of_block = j == 0;
         if (j + 1 < B.n) {
@@ -592,7 +600,7 @@ inline bool ws_ok(const void* ws, uint64_t bytes, uint32_t nb, uint64_t n_kv) {
 }
 
 inline int launch(const pbl_visible_in* in, pbl_visible_out* out, void* ws, uint64_t ws_bytes, uint32_t flags,
-                  bool size_only, hipStream_t st) {
+                  bool size_only, const uint64_t* cover, hipStream_t st) {
   const uint32_t allowed = PBL_VISIBLE_KEEP_OPERANDS | (size_only ? 0u : uint32_t(PBL_VISIBLE_SIZED));
   if (!args_ok(in, out, flags, allowed, size_only) || !ws_ok(ws, ws_bytes, in->n_blocks, in->n_kv)) return PBL_INVALID_ARG;
   const bool sized = (flags & PBL_VISIBLE_SIZED) != 0;
@@ -608,6 +616,7 @@ inline int launch(const pbl_visible_in* in, pbl_visible_out* out, void* ws, uint
   a.n_kv = n_kv;
   a.snapshot = in->snapshot;
   a.ws = static_cast<uint8_t*>(ws);
+  a.cover = cover;
   const Layout L = layout(nb, n_kv);
   if (hipMemsetAsync(out->result.totals, 0, sizeof(pbl_totals), st) != hipSuccess) return PBL_DEVICE_ERROR;
   const uint32_t t_grid = uint32_t(std::min<uint64_t>(L.nt, kGrid));
@@ -618,7 +627,8 @@ inline int launch(const pbl_visible_in* in, pbl_visible_out* out, void* ws, uint
     if (hipMemsetAsync(a.ws, 0, L.qst, st) != hipSuccess) return PBL_DEVICE_ERROR;
     if (nb) {
       seek::with_cmp(in->comparer, [&](auto c) {
-        hipLaunchKernelGGL(visible_classify_kernel<decltype(c)::value>, dim3(t_grid), dim3(kTPB), 0, st, a);
+        if (cover) hipLaunchKernelGGL((visible_classify_kernel<decltype(c)::value, true>), dim3(t_grid), dim3(kTPB), 0, st, a);
+        else hipLaunchKernelGGL((visible_classify_kernel<decltype(c)::value, false>), dim3(t_grid), dim3(kTPB), 0, st, a);
         return 0;
       });
       hipLaunchKernelGGL(visible_chunk_map_kernel, dim3(c_grid), dim3(kTPB), 0, st, a);
@@ -640,6 +650,10 @@ inline int launch(const pbl_visible_in* in, pbl_visible_out* out, void* ws, uint
   return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
 }
 
+// The sequential state machine; kCover: with the per-KV cover of rangedel.hip.
+template <bool kCover>
+int batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint32_t flags, const uint64_t* cover);
+
 }  // namespace visible
 }  // namespace pbl
 
@@ -651,15 +665,37 @@ uint64_t pbl_visible_workspace_bytes(uint32_t n_blocks, uint64_t n_kv) {
 
 int pbl_visible_size(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
                      uint32_t flags, void* stream) {
-  return pbl::visible::launch(in, out, workspace, workspace_bytes, flags, true, reinterpret_cast<hipStream_t>(stream));
+  return pbl::visible::launch(in, out, workspace, workspace_bytes, flags, true, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 int pbl_visible_batch(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
                       uint32_t flags, void* stream) {
-  return pbl::visible::launch(in, out, workspace, workspace_bytes, flags, false, reinterpret_cast<hipStream_t>(stream));
+  return pbl::visible::launch(in, out, workspace, workspace_bytes, flags, false, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int pbl_visible_size_rd(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
+                        uint32_t flags, const uint64_t* cover_seq, void* stream) {
+  return pbl::visible::launch(in, out, workspace, workspace_bytes, flags, true, cover_seq, reinterpret_cast<hipStream_t>(stream));
+}
+
+int pbl_visible_batch_rd(const pbl_visible_in* in, pbl_visible_out* out, void* workspace, uint64_t workspace_bytes,
+                         uint32_t flags, const uint64_t* cover_seq, void* stream) {
+  return pbl::visible::launch(in, out, workspace, workspace_bytes, flags, false, cover_seq, reinterpret_cast<hipStream_t>(stream));
 }
 
 int pbl_visible_batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint32_t flags) {
+  return pbl::visible::batch_host<false>(in, out, flags, nullptr);
+}
+
+int pbl_visible_batch_host_rd(const pbl_visible_in* in, pbl_visible_out* out, uint32_t flags, const uint64_t* cover_seq) {
+  return cover_seq ? pbl::visible::batch_host<true>(in, out, flags, cover_seq)
+                   : pbl::visible::batch_host<false>(in, out, flags, nullptr);
+}
+
+}  // extern "C"
+
+template <bool kCover>
+int pbl::visible::batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint32_t flags, const uint64_t* cover) {
   namespace M = pbl::visible;
   namespace K = pbl::seek;
   using R = pbl::cmp::HostReader;
@@ -680,6 +716,12 @@ int pbl_visible_batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint3
   auto walk = [&](uint32_t q, bool emit, uint64_t p0, Sizes* sz) -> uint32_t {
     const K::Block<R> B(V, q);
     const uint64_t* tr = D.trailer + B.kv0;
+    // rule 1: below the snapshot and under no newer range tombstone
+    auto seen = [&](uint32_t x) {
+      if (!M::is_visible(tr[x], in->snapshot)) return false;
+      if constexpr (kCover) return !(cover[B.kv0 + x] > (tr[x] >> 8));
+      return true;
+    };
     const uint32_t* vo = D.val_off + B.kv0 + q;
     const uint8_t* vb = D.val_bytes + D.blk_val_base[q];
     uint64_t p = p0;
@@ -735,7 +777,7 @@ int pbl_visible_batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint3
         if (pbl::cmp::key_cmp<R>(comparer, a, al, b, bl) != 0) break;
       }
       uint32_t h = j;
-      while (h < e && !M::is_visible(tr[h], in->snapshot)) h++;
+      while (h < e && !seen(h)) h++;
       bool ok;
       const uint32_t cls = h < e ? M::kind_class(tr[h], &ok) : uint32_t(M::kNone);
       if (cls == M::kSet) {
@@ -744,7 +786,7 @@ int pbl_visible_batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint3
         chain.clear();
         chain.push_back(h);
         for (uint32_t x = h + 1; x < e; x++) {
-          if (!M::is_visible(tr[x], in->snapshot)) continue;
+          if (!seen(x)) continue;
           const uint32_t c = M::kind_class(tr[x], &ok);
           if (c == M::kDel) break;
           chain.push_back(x);
@@ -839,6 +881,8 @@ int pbl_visible_batch_host(const pbl_visible_in* in, pbl_visible_out* out, uint3
   }
   return PBL_OK;
 }
+
+extern "C" {
 
 size_t pbl_visible_struct_layout(uint64_t* out, size_t cap) {
 #define PBL_OFF(T, f) uint64_t(offsetof(T, f))

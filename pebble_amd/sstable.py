@@ -51,6 +51,7 @@ INDEX_TYPE_PROP = b"rocksdb.block.based.table.index.type"
 KEY_SCHEMA_PROP = b"pebble.colblk.schema"
 PROPERTIES_NAME = b"rocksdb.properties"
 VALUE_INDEX_NAME = b"pebble.value_index"
+RANGE_DEL_NAME = b"rocksdb.range_del2"  # table.go metaRangeDelV2Name
 COMPARER_PROP = b"rocksdb.comparator"
 COMPARERS = {b"leveldb.BytewiseComparator": N.PBL_CMP_DEFAULT, b"pebble.internal.testkeys": N.PBL_CMP_TESTKEYS,
              b"cockroach_comparator": N.PBL_CMP_CRDB}
@@ -408,6 +409,23 @@ class Table:
             vb = self.value_blocks()
             if vb is not None:
                 d = resolve_values(d, vb)
+        return d
+
+    def range_dels(self) -> Optional[DecodedBatch]:
+        """The table's range-deletion fragments as a run (`pebble_amd.rangedel`):
+        the metaindex's "rocksdb.range_del2" block through the physical step and
+        the row decode (key = start, trailer = seq << 8 | 15, value = end), or
+        None when the table has none.  The columnar keyspan block
+        (colblk/keyspan.go) is not decoded: such a table raises."""
+        h = self.metaindex().get(RANGE_DEL_NAME)
+        if h is None:
+            return None
+        if self.footer.columnar:
+            raise DecodeError("the table holds range deletions in a colblk keyspan block, which is not decoded "
+                              "(colblk/keyspan.go): its reads would ignore them")
+        d = decode(self._handle_blocks([h], N.PBL_FMT_ROW))
+        if d.read_totals().status_mask:
+            raise DecodeError("range-del block corrupt")
         return d
 
     # -- positioning: batched seeks over the decoded table (pebble_amd.seek) --------

@@ -35,14 +35,25 @@ class VisibleResult:
 
 
 def visible(batch: DecodedBatch, *, comparer: int, snapshot: int = SEQNUM_MAX, keep_operands: bool = False,
-            stream=None) -> VisibleResult:
+            stream=None, cover: Optional[torch.Tensor] = None) -> VisibleResult:
     """Sizes first (pbl_visible_size), one read of the totals, exact allocation,
     then the emit with the statuses, sizes and roles the size call left in the
-    workspace (PBL_VISIBLE_SIZED): the input is classified once."""
+    workspace (PBL_VISIBLE_SIZED): the input is classified once.  `cover`
+    (`rangedel.cover`, int64 [n_kv]): a KV under a newer range tombstone is
+    invisible too (the _rd entry points); None is the call sequence without
+    range deletions."""
     dev = batch.trailer.device
     st = stream if stream is not None else torch.cuda.current_stream(dev)
     nb, n_kv = batch.n_blocks, _n_kv(batch)
     lib = N.lib()
+    if cover is not None:
+        if cover.dtype != torch.int64 or cover.device != dev or cover.numel() < n_kv or not cover.is_contiguous():
+            raise ValueError("cover: a contiguous int64 tensor of n_kv entries on the batch's device")
+        cp = ctypes.c_void_p(cover.data_ptr())
+        size_fn = lambda *a: lib.pbl_visible_size_rd(*a[:5], cp, a[5])  # noqa: E731
+        batch_fn = lambda *a: lib.pbl_visible_batch_rd(*a[:5], cp, a[5])  # noqa: E731
+    else:
+        size_fn, batch_fn = lib.pbl_visible_size, lib.pbl_visible_batch
     vin = N.VisibleInC(batch.c_struct(), nb, comparer, n_kv, snapshot)
     flags = N.PBL_VISIBLE_KEEP_OPERANDS if keep_operands else 0
     h = ctypes.c_void_p(st.cuda_stream)
@@ -51,7 +62,7 @@ def visible(batch: DecodedBatch, *, comparer: int, snapshot: int = SEQNUM_MAX, k
         sized = DecodedBatch.allocate(nb, Capacity(0, 0, 0, 0), dev, entry_off=False, restarts=False)
     wp = ctypes.c_void_p(ws.data_ptr())
     so = N.VisibleOutC(sized.c_struct(), None, None)
-    rc = lib.pbl_visible_size(ctypes.byref(vin), ctypes.byref(so), wp, ws.numel(), flags, h)
+    rc = size_fn(ctypes.byref(vin), ctypes.byref(so), wp, ws.numel(), flags, h)
     if rc != N.PBL_OK:
         raise DecodeError(f"pbl_visible_size failed: {N.STATUS_NAMES.get(rc, rc)}")
     st.synchronize()
@@ -63,7 +74,7 @@ def visible(batch: DecodedBatch, *, comparer: int, snapshot: int = SEQNUM_MAX, k
         src_kv = torch.empty(max(cap.kv, 1), dtype=torch.int64, device=dev)
         n_src = torch.empty(max(cap.kv, 1), dtype=torch.int32, device=dev)
     oo = N.VisibleOutC(out.c_struct(), src_kv.data_ptr(), n_src.data_ptr())
-    rc = lib.pbl_visible_batch(ctypes.byref(vin), ctypes.byref(oo), wp, ws.numel(), flags | N.PBL_VISIBLE_SIZED, h)
+    rc = batch_fn(ctypes.byref(vin), ctypes.byref(oo), wp, ws.numel(), flags | N.PBL_VISIBLE_SIZED, h)
     if rc != N.PBL_OK:
         raise DecodeError(f"pbl_visible_batch failed: {N.STATUS_NAMES.get(rc, rc)}")
     st.synchronize()
@@ -71,11 +82,17 @@ def visible(batch: DecodedBatch, *, comparer: int, snapshot: int = SEQNUM_MAX, k
     return VisibleResult(out, src_kv[: cap.kv], n_src[: cap.kv])
 
 
-def visible_host(host: dict, *, comparer: int, snapshot: int = SEQNUM_MAX, keep_operands: bool = False):
+def visible_host(host: dict, *, comparer: int, snapshot: int = SEQNUM_MAX, keep_operands: bool = False, cover=None):
     """The same view over host arrays (a `DecodedBatch.to_host()` dict) through
     pbl_visible_batch_host: (result dict in `to_host()`'s layout, src_kv uint64
-    [n_kv], n_src uint32 [n_kv])."""
+    [n_kv], n_src uint32 [n_kv]).  `cover` (`rangedel.cover_host`, uint64
+    [n_kv]): through pbl_visible_batch_host_rd."""
     lib = N.lib()
+    if cover is not None:
+        cover = np.ascontiguousarray(cover, np.uint64)
+        if cover.size < int(host["n_kv"]):
+            raise ValueError("cover: n_kv entries")
+        cover = cover if cover.size else np.zeros(1, np.uint64)
     n = len(host["blk_status"])
     keep: list = []
     vin = N.VisibleInC(host_struct(host, keep), n, comparer, 0, snapshot)
@@ -94,7 +111,10 @@ def visible_host(host: dict, *, comparer: int, snapshot: int = SEQNUM_MAX, keep_
         o.kv_cap, o.key_cap, o.val_cap = cap.kv, cap.key, cap.val
         vo = N.VisibleOutC(o, src_kv.ctypes.data if src_kv is not None else None,
                            n_src.ctypes.data if n_src is not None else None)
-        rc = lib.pbl_visible_batch_host(ctypes.byref(vin), ctypes.byref(vo), flags)
+        if cover is not None:
+            rc = lib.pbl_visible_batch_host_rd(ctypes.byref(vin), ctypes.byref(vo), flags, cover.ctypes.data)
+        else:
+            rc = lib.pbl_visible_batch_host(ctypes.byref(vin), ctypes.byref(vo), flags)
         if rc != N.PBL_OK:
             raise DecodeError(f"pbl_visible_batch_host failed: {N.STATUS_NAMES.get(rc, rc)}")
 
@@ -123,10 +143,41 @@ def visible_host(host: dict, *, comparer: int, snapshot: int = SEQNUM_MAX, keep_
 
 
 def read(tables, lowers: Sequence[Optional[bytes]], uppers: Sequence[Optional[bytes]], *, snapshot: int = SEQNUM_MAX,
-         hide_obsolete_points: bool = False, keep_operands: bool = False) -> VisibleResult:
+         hide_obsolete_points: bool = False, keep_operands: bool = False, range_dels=None, levels=None,
+         range_del_levels=None) -> VisibleResult:
     """`merge_scan` of the tables over the ranges, then `visible`: per range
     what an Iterator with those bounds over the tables returns going forward
-    (point keys; src_kv indexes the merge result)."""
+    (point keys; src_kv indexes the merge result).  Range deletions apply:
+    `range_dels` is a list of runs (`rangedel.build_set`), by default the
+    tables' own (`Table.range_dels()`); a caller passes its own for tombstones
+    that live elsewhere, for example a memtable's, fragmented by the caller.
+    With no tombstones the call sequence is the one without range deletions.
+    `levels` (one per table, smaller = shallower) applies the rule level by
+    level, as the reference does: a tombstone of a shallower level deletes
+    whatever the sequence numbers are.  It matters only where sequence numbers
+    are not ordered by level; without it the rule is the sequence-number one.
+    Caller-supplied runs then need `range_del_levels`, one per run."""
     tables = list(tables)
+    comparer = tables[0].comparer()
     merged = merge_scan(tables, lowers, uppers, hide_obsolete_points=hide_obsolete_points)
-    return visible(merged.batch, comparer=tables[0].comparer(), snapshot=snapshot, keep_operands=keep_operands)
+    if levels is not None and len(levels) != len(tables):
+        raise ValueError("levels: one per table")
+    if range_dels is None:
+        # (anything with comparer() and scan() serves as a table; one without range_dels() has none)
+        own = [(t.range_dels(), i) for i, t in enumerate(tables) if hasattr(t, "range_dels")]
+        range_dels = [r for r, _ in own if r is not None]
+        range_del_levels = [levels[i] for r, i in own if r is not None] if levels is not None else None
+    range_dels = list(range_dels)
+    if range_dels and (levels is None) != (range_del_levels is None):
+        raise ValueError("levels and range_del_levels go together")
+    cover = None
+    if range_dels:
+        from . import rangedel
+        rset = rangedel.build_set(range_dels, comparer, snapshot, levels=range_del_levels)
+        mask = int(rset.read_totals().status_mask)
+        if mask:
+            raise DecodeError("range deletions: " + ", ".join(N.STATUS_NAMES.get(b, str(b)) for b in range(32)
+                                                              if mask >> b & 1))
+        cover = rangedel.cover(rset, merged.batch, comparer, src_run=merged.src_run if levels is not None else None,
+                               run_levels=levels)
+    return visible(merged.batch, comparer=comparer, snapshot=snapshot, keep_operands=keep_operands, cover=cover)
