@@ -55,6 +55,11 @@ constexpr bool kLbL2 = PBL_LB_L2 != 0;
 //                             written only by the wave that resolves the chunk's
 //                             last block, and never waited for: a resolve that
 //                             finds one absent walks the chunk's records instead
+// Every launch starts from a zeroed header and zeroed rec[], pfx[][], wide[][]
+// and l2[] (ws_bytes in all): two memsets (totals, workspace) ahead of the
+// colblk kernels and of the two-pass row form; on the pool path (row and mixed
+// batches) row_prepare_kernel (rowblk_big.hip.h), each workgroup zeroing the
+// entries of the block ids it owns before it publishes into them.
 // All written and read with agent-scope relaxed 8-byte atomics (sc1): each word
 // carries its own state, so a reader that sees a record before the words it
 // announces simply polls those (no fences; MI355X_MICROARCH.md "Valid forms",
@@ -123,9 +128,12 @@ constexpr uint64_t kStampWords = 0;
 __host__ __device__ inline uint64_t ws_ids_offset(uint32_t n_blocks) {
   return ws_bytes(n_blocks) + kStampWords * 8ull * n_blocks;
 }
-// Then the big row blocks' lists (rowblk_big.hip.h): the sizes pass's tier-2
-// list (count at header word 5); the blocks the row kernel's own walk left
-// (count at word 6), for the values pass.
+// Then two id lists of the two-pass row form (rowblk_wave.hip.h): its dense
+// blocks (count at header word 5); the blocks whose key outgrew its emit's
+// stage (count at word 6), for the long-key values kernel.  The pool path
+// keeps no list here: row_prepare_kernel marks a big block it could not size
+// in blk_status[] (rowblk_big.hip.h), and the row kernel writes every big
+// block itself.
 __host__ __device__ inline uint64_t ws_redo_offset(uint32_t n_blocks) {
   return ws_ids_offset(n_blocks) + 4ull * n_blocks + 4ull * (n_blocks / kSplitChunk + 1) + 8;
 }

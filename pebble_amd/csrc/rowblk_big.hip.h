@@ -1,7 +1,9 @@
-// rowblk_big.hip.h — the passes for row blocks past the 32 KiB LDS stage:
-// big_block_sizes_kernel / big_block_sizes2_kernel before the decode launch,
-// big_block_values_kernel after it for what the row kernel left.  Each is the
-// general walk (rowblk_general.hip.h) over global memory.
+// rowblk_big.hip.h — row blocks past the 32 KiB LDS stage, and the launch that
+// prepares a pool-path batch: row_prepare_kernel clears the look-back state and
+// sizes those blocks ahead of the row kernel; the count walk and the publish
+// it shares with the row kernel's own second tier (block_big in
+// rowblk_pool.hip.h) and with the long-key kernels (rowblk_long.hip.h).  Each
+// walk is the general walk (rowblk_general.hip.h) over global memory.
 #pragma once
 
 #include "rowblk_core.hip.h"
@@ -12,7 +14,7 @@ namespace row {
 namespace rowc {
 
 #ifndef PBL_BIG_WIN
-#define PBL_BIG_WIN 8  // blocks per sizes tier-1 workgroup (the values pass's form: 126 us at 8, 170 at 16)
+#define PBL_BIG_WIN 8  // blocks per row_prepare_kernel workgroup (the values pass's form: 126 us at 8, 170 at 16)
 #endif
 #ifndef PBL_BIG_U
 #define PBL_BIG_U 8  // value granules per lane in flight (16: within noise on config 5)
@@ -21,23 +23,31 @@ namespace rowc {
 #define PBL_BIG_KEYBUF 8192
 #endif
 constexpr uint32_t kBigKeySmall = PBL_BIG_KEYBUF;  // the sizes tier-1 key buffer
-constexpr int kWsBigRedo = 5;  // header u32 [5]: sizes tier-2 blocks (their ids in the redo area, ws_redo_offset)
-constexpr int kWsBigPend = 6;  // header u32 [6]: blocks the row kernel did not write (ids at ws_pend_offset)
+constexpr int kWsBigRedo = 5;  // header u32 [5]: the two-pass row form's dense blocks (ids at ws_redo_offset)
+constexpr int kWsBigPend = 6;  // header u32 [6]: the two-pass row form's long-key blocks (ids at ws_pend_offset)
 constexpr int kWsBigLong = 7;  // header u32 [7]: a key past the 32 KiB buffer (rowblk_long.hip.h)
+// blk_status[b] of a block past the stage whose tier-1 walk needs more than
+// the small key buffer (or whose totals pass 4 GiB): not published yet.  The
+// wave of the row kernel that draws the block walks it again with a stage as
+// the key buffer (tier 2, block_big); with key spill slots
+// long_key_sizes2_kernel does, before the row kernel.  Never a final status:
+// whoever walks the block again replaces it.
+constexpr uint32_t kBigRedo = 0x80000000u | PBL_UNSUPPORTED;
 
-// Size pass for the blocks past the LDS stage (blen > kMaxFastLen), launched
-// ahead of the row kernel on the same stream.  Their count walk reads global
-// memory entry by entry; inside the pipeline it would hold back the look-back
-// of every later ticket.  Here all of them walk at once and publish their
+// Sizes of the blocks past the LDS stage (blen > kMaxFastLen), ahead of the row
+// kernel on the same stream.  Their count walk reads global memory entry by
+// entry; inside the pipeline it would hold back the look-back of every later
+// ticket.  In row_prepare_kernel all of them walk at once and publish their
 // aggregates, so the row kernel's block_big only resolves.  Same init checks
 // and the same general walk as a staged block's, so the aggregate is the one
-// the row kernel would compute.  Two tiers: tier 1 one one-wave
-// workgroup per PBL_BIG_WIN-block window with a kBigKeySmall key buffer; a
-// block whose walk needs more (PBL_UNSUPPORTED) is listed in the redo area and
-// walked by tier 2 with the whole 32 KiB buffer.  (Tier 1 was one workgroup per
-// 64 blocks, 4 per CU, with the 32 KiB buffer: config 5's 2195 big blocks took
-// 59 us, two to three serial walks per wave; 33 us in windows, 16 us without
-// one atomic per big block on a shared counter.)
+// the row kernel would compute.  Two tiers: tier 1 in row_prepare_kernel, one
+// one-wave workgroup per PBL_BIG_WIN-block window with a kBigKeySmall key
+// buffer; a block whose walk needs more (PBL_UNSUPPORTED) is marked kBigRedo
+// and walked with a whole 32 KiB stage by the wave of the row kernel that draws
+// its ticket (tier 2).  (Tier 1 was one workgroup per 64 blocks, 4 per CU, with
+// the 32 KiB buffer: config 5's 2195 big blocks took 59 us, two to three serial
+// walks per wave; 33 us in windows, 16 us without one atomic per big block on
+// a shared counter.)
 __device__ __forceinline__ void big_block_publish(const Args& A, uint32_t b, const SlowState& ss) {
   const uint32_t nb = A.in.n_blocks;
   uint64_t* lb_state = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(A.out.workspace) + kWsHeader);
@@ -72,90 +82,55 @@ __device__ __forceinline__ void big_block_count(const Args& A, uint32_t b, lptr<
                                   kPassCount, A.out, b, dummy, ss, spill, spillcap);
 }
 
-__global__ void __launch_bounds__(kWave) big_block_sizes_kernel(Args A) {
+// The one launch ahead of the row kernel on the pool path (row batches and
+// mixed batches): it clears what the two memsets cleared and does the sizes
+// tier 1.  Workgroup w owns the block ids of its windows: it zeroes their
+// entries of rec[], pfx[][] and wide[][] and the chunk records whose first block
+// it owns, workgroup 0 also the workspace header and *totals; then it walks its
+// windows' big blocks (row blocks only: a mixed batch's colblk blocks are the
+// colblk pipeline's) and publishes them.  A workgroup publishes only into
+// records it zeroed itself, after its zeroing stores have completed, so nothing
+// depends on the order in which workgroups run.  Nothing here adds to a header
+// counter or to *totals: workgroup 0 may be zeroing them at that moment.
+__global__ void __launch_bounds__(kWave) row_prepare_kernel(Args A) {
   __shared__ uint4 keybuf4[kBigKeySmall / 16];
+  static_assert(sizeof(pbl_totals) % 8 == 0 && kWsHeader / 8 <= kWave && sizeof(pbl_totals) / 8 <= kWave, "one store per lane");
   const uint32_t nb = A.in.n_blocks;
-  uint32_t* hdr = reinterpret_cast<uint32_t*>(A.out.workspace);
-  uint32_t* redo = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(A.out.workspace) + ws_redo_offset(nb));
+  const uint32_t l = lane_id();
+  uint64_t* ws = reinterpret_cast<uint64_t*>(A.out.workspace);
+  const LbPtrs P(ws + kWsHeader / 8, nb);
+  if (blockIdx.x == 0) {
+    if (l < kWsHeader / 8) st_agent(ws + l, 0);
+    if (l < sizeof(pbl_totals) / 8) st_agent(reinterpret_cast<uint64_t*>(A.out.totals) + l, 0);
+  }
   for (uint64_t base = uint64_t(blockIdx.x) * PBL_BIG_WIN; base < nb; base += uint64_t(gridDim.x) * PBL_BIG_WIN) {
-    const uint64_t bl = base + lane_id();
-    // (row blocks only: a mixed batch's colblk blocks are the colblk pipeline's)
-    uint64_t big = __ballot(lane_id() < PBL_BIG_WIN && bl < nb && to_glb(A.in.block_len)[bl] > kMaxFastLen &&
+    const uint32_t n = nb - base < PBL_BIG_WIN ? uint32_t(nb - base) : uint32_t(PBL_BIG_WIN);
+    for (uint32_t i = l; i < 2 * n; i += kWave) st_agent(P.rec + 2 * base + i, 0);
+    // (wide[][] follows pfx[][]: 2 * kNumComp arrays of n_blocks words)
+    for (uint32_t i = l; i < 2 * kNumComp * PBL_BIG_WIN; i += kWave) {
+      const uint32_t a = i / PBL_BIG_WIN, j = i % PBL_BIG_WIN;
+      if (j < n) st_agent(P.pfx + uint64_t(a) * nb + base + j, 0);
+    }
+    for (uint64_t c = (base + kL2Chunk - 1) / kL2Chunk + l; c * kL2Chunk < base + n; c += kWave) {
+      st_agent(P.l2 + 2 * c, 0);
+      st_agent(P.l2 + 2 * c + 1, 0);
+    }
+    const uint64_t bl = base + l;
+    uint64_t big = __ballot(l < PBL_BIG_WIN && bl < nb && to_glb(A.in.block_len)[bl] > kMaxFastLen &&
                             (!A.in.block_format || to_glb(A.in.block_format)[bl] == PBL_FMT_ROW));
+    // the zeroes have landed before a record of the window is published
+    if (big) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     while (big) {
       const uint32_t b = uint32_t(base) + uint32_t(__builtin_ctzll(big));
       big &= big - 1;
       SlowState ss;
       big_block_count(A, b, to_lds_ptr(reinterpret_cast<uint8_t*>(keybuf4)), kBigKeySmall, &ss);
       if (ss.status == PBL_UNSUPPORTED) {  // a key past the small buffer (or a total past 4 GiB): tier 2
-        if (lane_id() == 0) to_glb(redo)[g_atomic_add(hdr + kWsBigRedo, 1u)] = b;
+        if (l == 0) to_glb(A.out.blk_status)[b] = kBigRedo;
         continue;
       }
       big_block_publish(A, b, ss);
     }
-  }
-}
-
-// Tier 2's body.  kList (long_key_sizes2_kernel in rowblk_long.hip.h, launched
-// in its place for a workspace with key spill slots): a block whose walk
-// stopped at a key past the 32 KiB buffer is listed for tier 3 instead of
-// published (ids at ws_ent_offset, which the pool path leaves unused; their
-// count at header word kWsBigLong).  A block whose totals pass 4 GiB stays
-// PBL_UNSUPPORTED.  The two are told apart by the sums at the point where the
-// walk stopped: a block whose sums had already passed 4 GiB when it met the
-// long key is published as PBL_UNSUPPORTED without tier 3, which is its final
-// status unless a later entry is corrupt (the oracle would then report
-// PBL_CORRUPT_BOUNDS); that needs more than 4 GiB of decoded keys or values
-// ahead of a long key in one block, which no table holds.
-template <bool kList>
-__device__ __forceinline__ void big_block_sizes2_body(const Args& A, uint4* keybuf4) {
-  const uint32_t nb = A.in.n_blocks;
-  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(A.out.workspace);
-  const uint32_t n = __hip_atomic_load(to_glb(hdr) + kWsBigRedo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint32_t* redo = reinterpret_cast<const uint32_t*>(reinterpret_cast<uint8_t*>(A.out.workspace) +
-                                                           ws_redo_offset(nb));
-  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const uint32_t b = to_glb(redo)[i];
-    SlowState ss;
-    big_block_count(A, b, to_lds_ptr(reinterpret_cast<uint8_t*>(keybuf4)), uint32_t(kLdsBlkBytes), &ss);
-    if constexpr (kList) {
-      if (ss.status == PBL_UNSUPPORTED && !((ss.kb | ss.vb) >> 32)) {
-        uint32_t* lng = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(A.out.workspace) + ws_ent_offset(nb));
-        if (lane_id() == 0) to_glb(lng)[g_atomic_add(const_cast<uint32_t*>(hdr) + kWsBigLong, 1u)] = b;
-        continue;
-      }
-    }
-    big_block_publish(A, b, ss);
-  }
-}
-
-__global__ void __launch_bounds__(kWave) big_block_sizes2_kernel(Args A) {
-  __shared__ uint4 keybuf4[kLdsBlkBytes / 16];
-  big_block_sizes2_body<false>(A, keybuf4);
-}
-
-// Outputs of the blocks past the LDS stage.  The row kernel walks each one
-// itself once its look-back has resolved the block's bases (block_big in
-// rowblk_pool.hip.h: the wave's slot as the key buffer, the value copy hidden
-// behind the other waves' work); the blocks it could not (a key past the slot)
-// it lists, and this pass, launched after it on the same stream, walks them
-// with the whole 32 KiB key buffer.  8 value granules per lane in flight.
-__global__ void __launch_bounds__(kWave) big_block_values_kernel(Args A) {
-  __shared__ uint4 keybuf4[kLdsBlkBytes / 16];
-  const uint32_t nb = A.in.n_blocks;
-  const uint32_t* hdr = reinterpret_cast<const uint32_t*>(A.out.workspace);
-  const uint32_t n = __hip_atomic_load(to_glb(hdr) + kWsBigPend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint32_t* pend = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(A.out.workspace) +
-                                                           ws_pend_offset(nb));
-  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const uint32_t b = to_glb(pend)[i];
-    const uint32_t blen = A.in.block_len[b];
-    const uint64_t bases[kNumComp] = {A.out.blk_kv_base[b], A.out.blk_key_base[b], A.out.blk_val_base[b],
-                                      A.out.blk_rst_base ? A.out.blk_rst_base[b] : 0};
-    SlowState ss;
-    slow_walk_t<GlbBlk, PBL_BIG_U>(GlbBlk{to_glb(A.in.blocks + A.in.block_off[b]), blen}, blen, A.in.flags,
-                                    A.in.synthetic_seq_num, to_lds_ptr(reinterpret_cast<uint8_t*>(keybuf4)),
-                                    uint32_t(kLdsBlkBytes), kPassAll, A.out, b, bases, &ss);
   }
 }
 

@@ -5,7 +5,8 @@
 //
 // Kernels:
 //   rowblk_pool_kernel   (rowblk_pool.hip.h) the staging-pool kernel
-//   big_block_*_kernel   (rowblk_big.hip.h) blocks past the 32 KiB LDS stage
+//   row_prepare_kernel   (rowblk_big.hip.h) ahead of it: the look-back state
+//                        cleared, the blocks past the 32 KiB LDS stage sized
 //   long_key_*_kernel    (rowblk_long.hip.h) their blocks with a key past the 32
 //                        KiB key buffer, the key spilled to a workspace slot
 //   row_wave_*_kernel    (rowblk_wave.hip.h) PBL_BATCH_VARLEN batches in two
@@ -231,24 +232,25 @@ uint64_t persistent_grid(hipStream_t st, PersistentKernel k, const void* fn, uin
 #include "rowblk_long.hip.h"
 
 namespace {
-// The big row blocks' passes (rowblk_big.hip.h): sizes before the row kernel
-// (tier 1 a workgroup per PBL_BIG_WIN-block window, tier 2 over the blocks it
-// listed); after it, the outputs of the blocks the row kernel did not write.
-// The long-key kernels (a key past the 32 KiB buffer, spilled to a workspace
-// slot) follow each of them, when the caller's workspace holds slots
-// (pbl_workspace_bytes_for): sizes tier 3 over the blocks tier 2 listed, and
-// after the values pass the outputs of those blocks.
+// The launches around the row kernel on the pool path.  Ahead of it
+// row_prepare_kernel (rowblk_big.hip.h): the look-back state, the workspace
+// header and *totals cleared, the blocks past the 32 KiB stage sized, a
+// workgroup per PBL_BIG_WIN-block window; the row kernel does the rest itself.
+// Only a workspace that holds key spill slots (pbl_workspace_bytes_for) adds
+// the long-key kernels (a key past the 32 KiB buffer, spilled to a slot):
+// sizes tiers 2 and 3 before the row kernel, and after it the outputs of the
+// blocks tier 2 listed.
 bool has_spill_slots(const pbl::Args& a) {
   return pbl::ws_spill_slot_bytes(a.out.workspace_bytes, a.in.n_blocks) != 0;
 }
 
-void launch_big_sizes(const pbl::Args& a, hipStream_t st, uint32_t small) {
+void launch_prepare(const pbl::Args& a, hipStream_t st) {
   const uint32_t g1 = (a.in.n_blocks + PBL_BIG_WIN - 1) / PBL_BIG_WIN;
-  hipLaunchKernelGGL(pbl::row::rowc::big_block_sizes_kernel, dim3(g1), dim3(pbl::kWave), 0, st, a);
-  if (!has_spill_slots(a)) {
-    hipLaunchKernelGGL(pbl::row::rowc::big_block_sizes2_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
-    return;
-  }
+  hipLaunchKernelGGL(pbl::row::rowc::row_prepare_kernel, dim3(g1), dim3(pbl::kWave), 0, st, a);
+}
+
+void launch_long_sizes(const pbl::Args& a, hipStream_t st, uint32_t small) {
+  if (!has_spill_slots(a)) return;
   hipLaunchKernelGGL(pbl::row::rowc::long_key_sizes2_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
   hipLaunchKernelGGL(pbl::row::rowc::long_key_sizes_kernel, dim3(pbl::kLongKeyWgs), dim3(pbl::kWave), 0, st, a);
 }
@@ -257,11 +259,6 @@ void launch_long_values(const pbl::Args& a, hipStream_t st, uint64_t list_off, i
   if (has_spill_slots(a))
     hipLaunchKernelGGL(pbl::row::rowc::long_key_values_kernel, dim3(pbl::kLongKeyWgs), dim3(pbl::kWave), 0, st, a,
                        list_off, count_word);
-}
-
-void launch_big_values(const pbl::Args& a, hipStream_t st, uint32_t small) {
-  hipLaunchKernelGGL(pbl::row::rowc::big_block_values_kernel, dim3(small), dim3(pbl::kWave), 0, st, a);
-  launch_long_values(a, st, pbl::ws_ent_offset(a.in.n_blocks), pbl::row::rowc::kWsBigLong);
 }
 
 // The staging-pool kernel (rowblk_pool.hip.h): its persistent grid, and its
@@ -281,7 +278,8 @@ void launch_pool(const pbl::Args& a, hipStream_t st, bool hide, uint64_t grid, c
   });
 }
 
-// Row batches on the staging-pool kernel, with the big-block passes around it.
+// Row batches on the staging-pool kernel: two launches (and the long-key
+// kernels of a workspace with spill slots).
 int launch_row_pool(const pbl::Args& a, hipStream_t st, bool values) {
   const uint32_t nb = a.in.n_blocks;
   const bool hide = (a.in.flags & PBL_ROW_HIDE_OBSOLETE) && !(a.in.flags & PBL_ROW_RAW_KEYS);
@@ -289,15 +287,17 @@ int launch_row_pool(const pbl::Args& a, hipStream_t st, bool values) {
   const uint64_t grid = pool_grid(st, hide, nb, &cus);
   if (!grid) return PBL_DEVICE_ERROR;
   const uint32_t small = uint32_t(std::min<uint64_t>(nb, uint64_t(cus > 0 ? cus : 1) * 4));
-  launch_big_sizes(a, st, small);
+  launch_prepare(a, st);
+  launch_long_sizes(a, st, small);
   launch_pool(a, st, hide, grid, nullptr);
-  if (values) launch_big_values(a, st, small);
+  if (values) launch_long_values(a, st, pbl::ws_ent_offset(nb), pbl::row::rowc::kWsBigLong);
   return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
 }
 
-// Mixed batches: the ids split by format, the colblk sizes, the row kernel
-// over the row ids (with the big row blocks' size / value passes around it),
-// then the colblk blocks.
+// Mixed batches: the prepare launch (as for a row batch: it sizes the big row
+// blocks), the ids split by format (the split writes the header after the
+// prepare launch has cleared it, in stream order), the colblk sizes, the row
+// kernel over the row ids, then the colblk blocks.
 int launch_mixed(const pbl_block_batch* batch, const pbl::Args& a, hipStream_t st, bool values) {
   // HideObsoletePoints: colblk rows by their isObsolete bit, row entries by
   // their trailer's obsolete bit unless the keys are raw
@@ -308,6 +308,7 @@ int launch_mixed(const pbl_block_batch* batch, const pbl::Args& a, hipStream_t s
   uint32_t* ids = reinterpret_cast<uint32_t*>(ws + pbl::ws_ids_offset(nb));
   uint32_t* counts = ids + nb;
   const uint32_t nch = (nb + pbl::kSplitChunk - 1) / pbl::kSplitChunk;
+  launch_prepare(a, st);
   hipLaunchKernelGGL(pbl::row::mixed_split_count_kernel, dim3(nch), dim3(pbl::kTPB), 0, st, a, counts);
   hipLaunchKernelGGL(pbl::row::mixed_split_scatter_kernel, dim3(nch), dim3(pbl::kTPB), 0, st, a,
                      static_cast<const uint32_t*>(counts), nch, ids);
@@ -318,7 +319,7 @@ int launch_mixed(const pbl_block_batch* batch, const pbl::Args& a, hipStream_t s
   if (!g_c) return PBL_DEVICE_ERROR;
   const uint32_t small = uint32_t(std::min<uint64_t>(nb, uint64_t(cus > 0 ? cus : 1) * 4));
   const uint32_t* cids = static_cast<const uint32_t*>(ids);
-  launch_big_sizes(a, st, small);
+  launch_long_sizes(a, st, small);
   // (3) the colblk sizes, published (the staged wave form, colblk_wave.hip.h)
   const uint32_t g_cs = uint32_t(std::min<uint64_t>(nb, uint64_t(cus > 0 ? cus : 1) * 4 * PBL_CW_SWAVES));
   pbl::with_bool(hide, [&](auto h) {
@@ -343,7 +344,7 @@ int launch_mixed(const pbl_block_batch* batch, const pbl::Args& a, hipStream_t s
       hipLaunchKernelGGL(pbl::row::mixed_col_kernel<decltype(h)::value>, dim3(uint32_t(g_c)), dim3(pbl::kTPB), 0, st,
                          a, cids);
     });
-  if (values) launch_big_values(a, st, small);
+  if (values) launch_long_values(a, st, pbl::ws_ent_offset(nb), pbl::row::rowc::kWsBigLong);
   return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
 }
 
@@ -375,11 +376,18 @@ int launch_row_wave(const pbl::Args& a, hipStream_t st) {
 
 // A single-format row batch: the staging-pool kernel, or with
 // PBL_BATCH_VARLEN the two-pass form (PBL_KERNEL_POOL forces the pool).
+bool row_wave_path(uint32_t f) {
+  return (f & PBL_BATCH_VARLEN) && !(f & PBL_KERNEL_POOL) && pbl::row::rwave::sizes_without_keys(f);
+}
 int launch_row(const pbl::Args& a, hipStream_t st, bool values) {
-  const uint32_t f = a.in.flags;
-  if ((f & PBL_BATCH_VARLEN) && !(f & PBL_KERNEL_POOL) && pbl::row::rwave::sizes_without_keys(f))
-    return launch_row_wave(a, st);
-  return launch_row_pool(a, st, values);
+  return row_wave_path(a.in.flags) ? launch_row_wave(a, st) : launch_row_pool(a, st, values);
+}
+
+// Whether a batch with blocks runs the pool kernel (row and mixed batches but
+// for the two-pass row form): its prepare launch clears *totals and the
+// look-back state.  Every other path clears them with two memsets.
+bool pool_path(const pbl_block_batch* batch) {
+  return batch->block_format || (batch->format == PBL_FMT_ROW && !row_wave_path(batch->flags));
 }
 
 // The argument checks pbl_decode_batch and pbl_size_batch share: the batch and
@@ -412,13 +420,15 @@ int pbl_decode_batch_colblk(const pbl_block_batch* batch, pbl_decode_out* out, v
 int pbl_decode_batch(const pbl_block_batch* batch, pbl_decode_out* out, void* stream) {
   if (!per_block_args_ok(batch, out)) return PBL_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(out->totals, 0, sizeof(pbl_totals), st) != hipSuccess) return PBL_DEVICE_ERROR;
+  const bool args_ok = batch->n_blocks == 0 ||
+                       (block_args_ok(batch, out) && out->trailer && out->key_off && out->val_off && out->key_bytes &&
+                        out->val_bytes && (!out->tiering_span_id == !out->tiering_attr));
+  const bool prepared = batch->n_blocks != 0 && args_ok && pool_path(batch);
+  if (!prepared && hipMemsetAsync(out->totals, 0, sizeof(pbl_totals), st) != hipSuccess) return PBL_DEVICE_ERROR;
   if (batch->n_blocks == 0) return PBL_OK;
-  if (!block_args_ok(batch, out) || !out->trailer || !out->key_off || !out->val_off || !out->key_bytes || !out->val_bytes ||
-      (!out->tiering_span_id != !out->tiering_attr))
-    return PBL_INVALID_ARG;
+  if (!args_ok) return PBL_INVALID_ARG;
   if (!batch->block_format && batch->format != PBL_FMT_ROW) return pbl_decode_batch_colblk(batch, out, stream);
-  if (hipMemsetAsync(out->workspace, 0, pbl::ws_bytes(batch->n_blocks), st) != hipSuccess)
+  if (!prepared && hipMemsetAsync(out->workspace, 0, pbl::ws_bytes(batch->n_blocks), st) != hipSuccess)
     return PBL_DEVICE_ERROR;
   pbl::Args a;
   a.in = *batch;
@@ -450,8 +460,10 @@ int pbl_size_batch(const pbl_block_batch* batch, pbl_decode_out* out, void* stre
   o.tiering_span_id = nullptr;
   o.tiering_attr = nullptr;
   o.kv_cap = o.key_cap = o.val_cap = o.rst_cap = 0;
-  if (hipMemsetAsync(o.totals, 0, sizeof(pbl_totals), st) != hipSuccess) return PBL_DEVICE_ERROR;
-  if (hipMemsetAsync(o.workspace, 0, pbl::ws_bytes(batch->n_blocks), st) != hipSuccess) return PBL_DEVICE_ERROR;
+  if (!pool_path(batch)) {
+    if (hipMemsetAsync(o.totals, 0, sizeof(pbl_totals), st) != hipSuccess) return PBL_DEVICE_ERROR;
+    if (hipMemsetAsync(o.workspace, 0, pbl::ws_bytes(batch->n_blocks), st) != hipSuccess) return PBL_DEVICE_ERROR;
+  }
   pbl::Args a;
   a.in = *batch;
   a.out = o;
@@ -460,7 +472,7 @@ int pbl_size_batch(const pbl_block_batch* batch, pbl_decode_out* out, void* stre
     rc = pbl_decode_batch_colblk(batch, &o, stream);
   } else {
     // the launch sequence of pbl_decode_batch (whose checks require output
-    // pointers), minus the big-block value pass
+    // pointers), minus the long-key values kernel
     rc = batch->block_format ? launch_mixed(batch, a, st, false) : launch_row(a, st, false);
   }
   if (rc != PBL_OK) return rc;

@@ -32,12 +32,42 @@ __device__ __forceinline__ LongSlot long_slot(const Args& A) {
                   cap};
 }
 
-// Sizes tier 2 for a workspace with slots: big_block_sizes2_kernel's body in
-// its listing form (rowblk_big.hip.h).  A kernel of its own, so that the one a
-// workspace without slots runs stays as it was.
+// Sizes tier 2 for a workspace with slots, between row_prepare_kernel and the
+// row kernel (without slots the row kernel's block_big does tier 2 itself):
+// every block that tier 1 marked kBigRedo (rowblk_big.hip.h) is walked with the
+// whole 32 KiB buffer.  A block whose walk stopped at a key past that buffer
+// is listed for tier 3 instead of published (ids at ws_ent_offset, which the
+// pool path leaves unused; their count at header word kWsBigLong).  A block
+// whose totals pass 4 GiB stays PBL_UNSUPPORTED.  The two are told apart by the
+// sums at the point where the walk stopped: a block whose sums had already
+// passed 4 GiB when it met the long key is published as PBL_UNSUPPORTED without
+// tier 3, which is its final status unless a later entry is corrupt (the
+// oracle would then report PBL_CORRUPT_BOUNDS); that needs more than 4 GiB of
+// decoded keys or values ahead of a long key in one block, which no table
+// holds.  The marks are found by a scan of the batch, kWave ids per step: tier
+// 1 keeps no list, because nothing in it may add to a header counter.
 __global__ void __launch_bounds__(kWave) long_key_sizes2_kernel(Args A) {
   __shared__ uint4 keybuf4[kLdsBlkBytes / 16];
-  big_block_sizes2_body<true>(A, keybuf4);
+  const uint32_t nb = A.in.n_blocks;
+  uint32_t* hdr = reinterpret_cast<uint32_t*>(A.out.workspace);
+  uint32_t* lng = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(A.out.workspace) + ws_ent_offset(nb));
+  for (uint64_t base = uint64_t(blockIdx.x) * kWave; base < nb; base += uint64_t(gridDim.x) * kWave) {
+    const uint64_t bl = base + lane_id();
+    uint64_t redo = __ballot(bl < nb && to_glb(A.in.block_len)[bl] > kMaxFastLen &&
+                             (!A.in.block_format || to_glb(A.in.block_format)[bl] == PBL_FMT_ROW) &&
+                             to_glb(A.out.blk_status)[bl] == kBigRedo);
+    while (redo) {
+      const uint32_t b = uint32_t(base) + uint32_t(__builtin_ctzll(redo));
+      redo &= redo - 1;
+      SlowState ss;
+      big_block_count(A, b, to_lds_ptr(reinterpret_cast<uint8_t*>(keybuf4)), uint32_t(kLdsBlkBytes), &ss);
+      if (ss.status == PBL_UNSUPPORTED && !((ss.kb | ss.vb) >> 32)) {
+        if (lane_id() == 0) to_glb(lng)[g_atomic_add(hdr + kWsBigLong, 1u)] = b;
+        continue;
+      }
+      big_block_publish(A, b, ss);
+    }
+  }
 }
 
 // Sizes tier 3: the blocks tier 2 listed, sized with the spill form and
@@ -66,12 +96,11 @@ __global__ void __launch_bounds__(kWave) long_key_sizes_kernel(Args A) {
 // its emit listed).  A listed block's bases are final; one that is not PBL_OK
 // (an overflow, a key past its slot) has no outputs.  The walk rewrites what
 // an earlier walk of the block wrote up to its long key.  On the pool path
-// there are two of those: block_big's with the wave's slot, which lists the
-// block for big_block_values_kernel, and that kernel's with the 32 KiB buffer;
-// both stop at the long key, inside the block's own output range.  The second
-// is wasted work, left as it is: skipping it would put a lookup of tier 3's
-// list into block_big, that is into the pool kernel every batch runs, to save
-// one partial walk per long-key block on a cold path.
+// there are two of those, both block_big's: with the wave's slot, then with a
+// 32 KiB stage; both stop at the long key, inside the block's own output range.
+// The second is wasted work, left as it is: skipping it would put a lookup of
+// tier 3's list into block_big, that is into the pool kernel every batch runs,
+// to save one partial walk per long-key block on a cold path.
 __global__ void __launch_bounds__(kWave) long_key_values_kernel(Args A, uint64_t list_off, int count_word) {
   __shared__ uint4 keybuf4[kLdsBlkBytes / 16];
   const pbl_decode_out& O = A.out;

@@ -45,8 +45,9 @@
 // Blocks outside the fast-path limits (more entries than a slot holds, keys
 // past kMaxKl, 3-byte header varints, ...) take the wave-serial general walk
 // (rowblk_general.hip.h) on the staged bytes; blocks past kMaxFastLen are sized
-// by big_block_sizes_kernel before this launch and written by the wave that
-// draws their ticket (block_big; rowblk_big.hip.h).  Results are identical on
+// by row_prepare_kernel before this launch (rowblk_big.hip.h; the few it leaves,
+// by the wave that draws them, with its stage as the key buffer) and written by
+// the wave that draws their ticket (block_big).  Results are identical on
 // every path.
 //
 // Semantics: cockroachdb/pebble sstable/rowblk/rowblk_iter.go — Init :241-276,
@@ -1146,16 +1147,18 @@ __device__ __forceinline__ void copy_long_values(const uint32_t* vp, gptr<const 
 }
 
 // Take a free stage (lane 0 spins on the workgroup's mask); returns its index.
-template <bool kHide>
-__device__ __forceinline__ uint32_t acquire(PoolLds<kHide>& L) {
+// (The mask by pointer: block_big, out of line and not a template, takes and
+// returns stages too.)
+template <class M>
+__device__ __forceinline__ uint32_t acquire_stage(M* free_mask) {
   uint32_t s = 0;
   if (lane_id() == 0) {
     for (;;) {
-      const uint32_t m = __hip_atomic_load(&L.free_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const uint32_t m = __hip_atomic_load(free_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (m) {
         const uint32_t c = uint32_t(__builtin_ctz(m));
         const uint32_t old =
-            __hip_atomic_fetch_and(&L.free_mask, ~(1u << c), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_and(free_mask, ~(1u << c), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (old & (1u << c)) {
           s = c;
           break;
@@ -1169,6 +1172,10 @@ __device__ __forceinline__ uint32_t acquire(PoolLds<kHide>& L) {
   // waiting for a stage: it wins issue arbitration against the emitting waves
   if (PBL_POOL_PRIO) __builtin_amdgcn_s_setprio(PBL_POOL_PRIO);
   return __builtin_amdgcn_readfirstlane(__shfl(s, 0, kWave));
+}
+template <bool kHide>
+__device__ __forceinline__ uint32_t acquire(PoolLds<kHide>& L) {
+  return acquire_stage(&L.free_mask);
 }
 
 // Take a free stage if there is one: one read of the mask and one fetch_and,
@@ -1192,12 +1199,16 @@ __device__ __forceinline__ int32_t try_acquire(PoolLds<kHide>& L) {
 
 // Return stage s to the pool once every LDS read of it has completed.
 // `drop_prio`: the wave's issue priority falls back to the emit's.
-template <bool kHide>
-__device__ __forceinline__ void release(PoolLds<kHide>& L, uint32_t s, bool drop_prio = true) {
+template <class M>
+__device__ __forceinline__ void release_stage(M* free_mask, uint32_t s, bool drop_prio = true) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   wave_sync();
-  if (lane_id() == 0) __hip_atomic_fetch_or(&L.free_mask, 1u << s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  if (lane_id() == 0) __hip_atomic_fetch_or(free_mask, 1u << s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   if (PBL_POOL_PRIO && drop_prio) __builtin_amdgcn_s_setprio(0);
+}
+template <bool kHide>
+__device__ __forceinline__ void release(PoolLds<kHide>& L, uint32_t s, bool drop_prio = true) {
+  release_stage(&L.free_mask, s, drop_prio);
 }
 
 // The block [boff, boff + blen) into stage S by LDS-DMA (granule g of the 16-B
@@ -1249,23 +1260,46 @@ __device__ __noinline__ void block_slow(Stage& S, uint8_t* keybuf, uint32_t keyc
   if (l == 0) write_block_meta(O, b, nb, st2, excl, agg, true);
 }
 
-// A block past the stage: big_block_sizes_kernel walked it, published its
-// aggregate and left {status, counts} in its block-metadata slots.  Once its
-// bases resolve, the wave walks it from global memory and writes its outputs,
-// its slot as the key buffer; a key past the slot lists the block for
-// big_block_values_kernel (after this launch).  (Config 5: 2195 big blocks,
-// one 48 KB value each; the separate values pass took 87 us.)  Out of line.
+// A block past the stage (stage s held on entry, released here).
+// row_prepare_kernel walked it, published its aggregate and left {status,
+// counts} in its block-metadata slots; or it marked the block kBigRedo (a key
+// past its small buffer), and then this wave, which still holds its stage,
+// runs the count walk with that stage as the 32 KiB key buffer and publishes
+// (sizes tier 2), and only then lets the stage go.  Once the block's bases
+// resolve, the wave walks it from global memory and writes its outputs, its
+// slot as the key buffer; at a key past the slot it takes a stage again and
+// repeats the walk with that as the key buffer.  (Config 5: 2195 big blocks,
+// one 48 KB value each; a separate values pass took 87 us.)  Out of line.
+// `stages`, `free_mask`: the workgroup's pool.
 __device__ __noinline__ void block_big(const Args A, uint32_t b, uint64_t boff, uint32_t blen, uint8_t* keybuf,
-                                       uint32_t keycap) {
+                                       uint32_t keycap, Stage* stages, uint32_t* free_mask, uint32_t s) {
   const int l = lane_id();
   const uint32_t nb = A.in.n_blocks;
   const pbl_decode_out& O = A.out;
+  const lptr<uint32_t> fm = to_lds_ptr(free_mask);
   uint64_t* lb_state = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(O.workspace) + kWsHeader);
-  const uint32_t st0 = to_glb(O.blk_status)[b];
+  uint32_t st0 = to_glb(O.blk_status)[b];
+  uint64_t agg[kNumComp];
+  if (st0 == rowc::kBigRedo) {
+    SlowState ss;
+    rowc::big_block_count(A, b, to_lds_ptr(reinterpret_cast<uint8_t*>(stages[s].x)), uint32_t(kLdsBlkBytes), &ss);
+    rowc::big_block_publish(A, b, ss);
+    release_stage(fm, s);
+    st0 = ss.status;
+    const bool ok2 = st0 == PBL_OK;
+    agg[0] = ok2 ? ss.nkv : 0;
+    agg[1] = ok2 ? ss.kb : 0;
+    agg[2] = ok2 ? ss.vb : 0;
+    agg[3] = ok2 ? ss.nr : 0;
+  } else {
+    release_stage(fm, s);
+    const bool ok1 = st0 == PBL_OK;
+    agg[0] = ok1 ? to_glb(O.blk_kv_base)[b] : 0;
+    agg[1] = ok1 ? to_glb(O.blk_key_base)[b] : 0;
+    agg[2] = ok1 ? to_glb(O.blk_val_base)[b] : 0;
+    agg[3] = ok1 ? uint64_t(GlbBlk{to_glb(A.in.blocks + boff), blen}.le32(blen - 4)) : 0;
+  }
   const bool okk = st0 == PBL_OK;
-  const uint64_t agg[kNumComp] = {okk ? to_glb(O.blk_kv_base)[b] : 0, okk ? to_glb(O.blk_key_base)[b] : 0,
-                                  okk ? to_glb(O.blk_val_base)[b] : 0,
-                                  okk ? uint64_t(GlbBlk{to_glb(A.in.blocks + boff), blen}.le32(blen - 4)) : 0};
   uint64_t excl[kNumComp];
   lb_resolve<kLbWin, kLbL2, kPoolLbF>(lb_state, nb, b, agg, excl, &O.totals->status_mask);
   uint32_t st2 = st0;
@@ -1278,14 +1312,26 @@ __device__ __noinline__ void block_big(const Args A, uint32_t b, uint64_t boff, 
     write_block_meta(O, b, nb, st2, excl, agg, true);
   }
   if (st2 == PBL_OK) {
+    // the wave has published and resolved: it may wait for a stage, no stage
+    // holder ever waits on it
+    lptr<uint8_t> kb = to_lds_ptr(keybuf);
+    bool staged = false;
+    uint32_t s2 = 0;
     SlowState ss;
-    slow_walk_t<GlbBlk, PBL_BIG_U>(GlbBlk{to_glb(A.in.blocks + boff), blen}, blen, A.in.flags,
-                                    A.in.synthetic_seq_num, to_lds_ptr(keybuf), keycap, kPassAll, O, b, excl, &ss);
-    if (ss.status == PBL_UNSUPPORTED && l == 0) {  // a key past the slot: the values pass rewrites the block
-      uint32_t* hdr = reinterpret_cast<uint32_t*>(O.workspace);
-      uint32_t* pend = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(O.workspace) + ws_pend_offset(nb));
-      to_glb(pend)[g_atomic_add(hdr + rowc::kWsBigPend, 1u)] = b;
-    } else if (ss.status != PBL_OK && l == 0) {
+    for (;;) {
+      slow_walk_t<GlbBlk, PBL_BIG_U>(GlbBlk{to_glb(A.in.blocks + boff), blen}, blen, A.in.flags,
+                                      A.in.synthetic_seq_num, kb, keycap, kPassAll, O, b, excl, &ss);
+      // a key past the slot: once more with a stage, which rewrites the block
+      // (a key past the stage too: the block's outputs are the long-key
+      // kernels', rowblk_long.hip.h)
+      if (staged || ss.status != PBL_UNSUPPORTED) break;
+      s2 = acquire_stage(fm);
+      staged = true;
+      kb = to_lds_ptr(reinterpret_cast<uint8_t*>(stages[s2].x));
+      keycap = uint32_t(kLdsBlkBytes);
+    }
+    if (staged) release_stage(fm, s2);
+    if (!staged && ss.status != PBL_OK && l == 0) {
       // the same walk as the sizes pass over the same bytes cannot disagree
       // with it; if it ever did, the block reports the walk's status
       to_glb(O.blk_status)[b] = ss.status;
@@ -1326,8 +1372,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
   P.status = PBL_OK;
 
   if (blen > kMaxFastLen) {
-    release(L, s);
-    block_big(A, b, boff, blen, reinterpret_cast<uint8_t*>(&W), uint32_t(sizeof(W)));
+    block_big(A, b, boff, blen, reinterpret_cast<uint8_t*>(&W), uint32_t(sizeof(W)), L.st, &L.free_mask, s);
     return P;
   }
   PSTAMP(A, b, 1, l == 0);
@@ -1439,7 +1484,7 @@ __device__ __forceinline__ void prefetch(PoolLds<kHide>& L, const Args& A, const
   if (ids) t = __builtin_amdgcn_readfirstlane(to_glb(ids)[t]);
   const uint64_t boff = to_glb(A.in.block_off)[t];
   const uint32_t blen = to_glb(A.in.block_len)[t];
-  // (a block past the stage is handed on as it is: block_big lets the stage go first)
+  // (a block past the stage is handed on as it is: block_big lets the stage go before its look-back)
   const bool staged = blen <= kMaxFastLen;
   X.t = t;
   X.w = uint32_t(s) | kNextHave | (staged ? kNextStaged : 0u);
@@ -1628,6 +1673,19 @@ __device__ __forceinline__ void block_emit(const Pend& P, const Slot<kHide>& W, 
 //    holds a stage (and so reaches its publish by the above) or has published;
 //    every poll of it (lb_finish's single-lane poll, lb_poll) is bounded by the
 //    spin cap and ends in PBL_TIMEOUT;
+//  - a block past the stage that row_prepare_kernel left unsized (kBigRedo) is
+//    sized by the wave that draws it, which still holds the ticket's stage: it
+//    runs the count walk (its own memory operations only) with that stage as
+//    the key buffer, publishes, and only then lets the stage go, so the first
+//    two points hold for it as for a staged block;
+//  - block_big's second write walk (a key past the slot) waits for a stage
+//    after the wave has published AND resolved: it holds no stage and no
+//    unpublished ticket while it waits, and no stage holder waits on it (a
+//    holder waits on its own memory operations, or in block_slow's look-back on
+//    smaller tickets, which this wave's publish already satisfies); every
+//    holder therefore runs on to its release, and the waiting wave gets a
+//    stage.  With every wave of a workgroup in that wait at once, no stage is
+//    held and the first to look takes one;
 //  - the two-level form (PBL_LB_L2) adds two stores and no wait: the wave that
 //    resolves a chunk's last block stores the chunk's summed aggregate after
 //    its first window (only from records it has already loaded) and the
