@@ -1276,6 +1276,94 @@ int pbl_visible_batch_host_rd(const pbl_visible_in* in, pbl_visible_out* out, ui
  * unchanged; ABI version 9 stands). */
 size_t pbl_rangedel_struct_layout(uint64_t* out, size_t cap);
 
+/* ---- columnar keyspan blocks, on the device --------------
+ * A columnar table (Pebblev5 and later) keeps its range deletions, and its range
+ * keys, in colblk keyspan blocks (sstable/colblk/keyspan.go).  These entry
+ * points decode a batch of such blocks into RUNS as defined above: one result
+ * block per input block, which pbl_rangedel_set, the host iterator and the
+ * per-block seeks read unchanged.  batch->format, flags and block_format are
+ * ignored; synthetic_seq_num applies (keyspan.go:599-603).
+ *
+ * Block layout (KeyspanDecoder.Init, keyspan.go:234-248): bytes 0-3 B, the
+ * number of boundary user keys (LE32); from byte 4 the colblk header (custom
+ * header size 4) with 5 columns and R rows, one per keyspan.Key; column 0
+ * RawBytes with B rows, the boundary keys; column 1 Uint with B rows, idx[], the
+ * first key row of the span that starts at each boundary; column 2 Uint with R
+ * rows, the trailers; columns 3 and 4 RawBytes with R rows, the suffixes and the
+ * values; one trailing padding byte.  Every DecodeColumn check applies, the end
+ * of one column being the start of the next.
+ *
+ * The forward walk (First(); Next()...; keyspan.go:478-543): span s, 0 <= s <
+ * B-1, is [boundary[s], boundary[s+1]) and holds key rows idx[s] .. idx[s+1]-1.
+ * A span without rows is a gap and is passed over; an empty first span is
+ * legal.  One KV comes out per key row j of span s: key = boundary[s], value =
+ * boundary[s+1], trailer = column 2's word (or synthetic_seq_num << 8 | kind),
+ * kv_flags 0, entry_off = j; there are no restarts (blk_rst_base all zero,
+ * totals.n_restarts 0).  B < 2 is an OK block without KVs.  Rows before idx[0]
+ * and from idx[B-1] on cannot be reached in the reference and are not output.
+ *
+ * blk_status: header or column directory failures, a column count other than
+ * 5: PBL_CORRUPT_COLBLK_HEADER.  With B >= 2, PBL_CORRUPT_BOUNDS for: a boundary
+ * offset that decreases; idx[s] > idx[s+1]; idx[B-1] > R; the last span empty;
+ * two empty spans in a row; among the rows that are output, idx[0] .. idx[B-1]-1,
+ * a suffix or value offset that decreases, or the end of the last such slice
+ * (the offset of row idx[B-1]) past the column's own last offset, that of row
+ * R, which is the only one DecodeColumn bounds (rows that no span reaches are
+ * not looked at: the reference never reads them); B larger than the block's
+ * length (its idx[] would be constant).  The reference finds these lazily, and panics on a decreasing or
+ * out-of-range index; here they are reported for the whole block, which then
+ * holds no KVs.  More than 4 GiB - 1 of key or of value bytes in one block:
+ * PBL_UNSUPPORTED.  A block whose boundaries do not fit the workspace
+ * (total_boundaries was too small): PBL_INVALID_ARG in blk_status.
+ *
+ * `extra` (optional, NULL allowed) receives per KV what a range key needs: the
+ * start boundary index (span[kv]) and the keyspan.Key's Suffix and Value (not
+ * the run's value, which is the end key), laid out as keys are: suffix j of
+ * block b = suffix_bytes[blk_suffix_base[b] + suffix_off[o] .. + suffix_off[o+1])
+ * with o = blk_kv_base[b] + b + j; likewise value_*.
+ *
+ * total_boundaries: the sum over the blocks of min(B, block_len), B being each
+ * block's first four bytes (the caller reads them; a smaller number only makes
+ * blocks PBL_INVALID_ARG).  The workspace (DEVICE, 16-byte aligned,
+ * pbl_keyspan_workspace_bytes bytes) serves one call at a time.  The blocks
+ * must be readable up to the next 16-byte boundary after every block, as for
+ * every batch.  pbl_keyspan_size writes only blk_{kv,key,val,rst}_base,
+ * blk_status and totals (and extra's two base arrays): exact sizes for the
+ * allocation.  pbl_keyspan_decode writes everything; when a capacity is
+ * exceeded (extra's included) it writes the sizes, no bytes, and PBL_OVERFLOW in
+ * totals.status_mask.  key_off / val_off / suffix_off / value_off hold
+ * kv_cap + n_blocks entries.  Stream-ordered, no host synchronisation.
+ *
+ * pbl_keyspan_decode_host is the same over HOST arrays by another algorithm:
+ * the reference's sequential walk span by span (gatherKeysForward,
+ * materializeSpan), with its own column decoders.  With out->key_off NULL it
+ * sizes only.
+ *
+ * PBL_INVALID_ARG, before any device call: NULL batch / out or a needed array,
+ * synthetic_seq_num >= 2^56, a workspace that is NULL, not 16-byte aligned or
+ * too short.
+ */
+typedef struct pbl_keyspan_extra {
+  uint32_t* span;            /* [kv_cap] the start boundary index of each KV's span */
+  uint32_t* suffix_off;      /* [kv_cap + n_blocks] block-relative suffix offsets  */
+  uint32_t* value_off;       /* [kv_cap + n_blocks] block-relative value offsets   */
+  uint8_t* suffix_bytes;     /* [suffix_cap]                                       */
+  uint8_t* value_bytes;      /* [value_cap]                                        */
+  uint64_t* blk_suffix_base; /* [n_blocks+1]                                       */
+  uint64_t* blk_value_base;  /* [n_blocks+1]                                       */
+  uint64_t suffix_cap, value_cap;
+} pbl_keyspan_extra;
+
+uint64_t pbl_keyspan_workspace_bytes(uint32_t n_blocks, uint64_t total_boundaries);
+int pbl_keyspan_size(const pbl_block_batch* batch, uint64_t total_boundaries, pbl_decode_out* out,
+                     pbl_keyspan_extra* extra, void* workspace, uint64_t workspace_bytes, void* stream);
+int pbl_keyspan_decode(const pbl_block_batch* batch, uint64_t total_boundaries, pbl_decode_out* out,
+                       pbl_keyspan_extra* extra, void* workspace, uint64_t workspace_bytes, void* stream);
+int pbl_keyspan_decode_host(const pbl_block_batch* batch, pbl_decode_out* out, pbl_keyspan_extra* extra);
+/* sizeof(pbl_keyspan_extra), its 9 field offsets (the other layout lists are
+ * unchanged; ABI version 9 stands). */
+size_t pbl_keyspan_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,13 @@ class RangedelRunsC(ctypes.Structure):  # pbl_rangedel_runs
                 ("level", ctypes.POINTER(ctypes.c_uint8))]
 
 
+# columnar keyspan blocks (pbl_keyspan_decode)
+class KeyspanExtraC(ctypes.Structure):  # pbl_keyspan_extra
+    _fields_ = [("span", _vp), ("suffix_off", _vp), ("value_off", _vp), ("suffix_bytes", _vp), ("value_bytes", _vp),
+                ("blk_suffix_base", _vp), ("blk_value_base", _vp), ("suffix_cap", ctypes.c_uint64),
+                ("value_cap", ctypes.c_uint64)]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -332,6 +339,14 @@ SIGNATURES = {
     "pbl_visible_batch_host_rd": (ctypes.c_int, [ctypes.POINTER(VisibleInC), ctypes.POINTER(VisibleOutC),
                                                  ctypes.c_uint32, _vp]),
     "pbl_rangedel_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_keyspan_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint64]),
+    "pbl_keyspan_size": (ctypes.c_int, [ctypes.POINTER(BlockBatchC), ctypes.c_uint64, ctypes.POINTER(DecodeOutC),
+                                        ctypes.POINTER(KeyspanExtraC), _vp, ctypes.c_uint64, _vp]),
+    "pbl_keyspan_decode": (ctypes.c_int, [ctypes.POINTER(BlockBatchC), ctypes.c_uint64, ctypes.POINTER(DecodeOutC),
+                                          ctypes.POINTER(KeyspanExtraC), _vp, ctypes.c_uint64, _vp]),
+    "pbl_keyspan_decode_host": (ctypes.c_int, [ctypes.POINTER(BlockBatchC), ctypes.POINTER(DecodeOutC),
+                                               ctypes.POINTER(KeyspanExtraC)]),
+    "pbl_keyspan_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

@@ -415,14 +415,19 @@ class Table:
         """The table's range-deletion fragments as a run (`pebble_amd.rangedel`):
         the metaindex's "rocksdb.range_del2" block through the physical step and
         the row decode (key = start, trailer = seq << 8 | 15, value = end), or
-        None when the table has none.  The columnar keyspan block
-        (colblk/keyspan.go) is not decoded: such a table raises."""
+        None when the table has none.  A columnar table keeps them in a colblk
+        keyspan block (colblk/keyspan.go), which `pebble_amd.keyspan.decode`
+        turns into the same run."""
         h = self.metaindex().get(RANGE_DEL_NAME)
         if h is None:
             return None
         if self.footer.columnar:
-            raise DecodeError("the table holds range deletions in a colblk keyspan block, which is not decoded "
-                              "(colblk/keyspan.go): its reads would ignore them")
+            from .keyspan import decode as keyspan_decode
+            d = keyspan_decode(self._handle_blocks([h], N.PBL_FMT_ROW))
+            if d.read_totals().status_mask:
+                raise DecodeError("range-del keyspan block corrupt "
+                                  f"({N.STATUS_NAMES.get(int(d.blk_status[0].item()), '?')})")
+            return d
         d = decode(self._handle_blocks([h], N.PBL_FMT_ROW))
         if d.read_totals().status_mask:
             raise DecodeError("range-del block corrupt")
