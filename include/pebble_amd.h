@@ -1364,6 +1364,136 @@ int pbl_keyspan_decode_host(const pbl_block_batch* batch, pbl_decode_out* out, p
  * unchanged; ABI version 9 stands). */
 size_t pbl_keyspan_struct_layout(uint64_t* out, size_t cap);
 
+/* ---- range keys in the read path --------------------------
+ * What a bounded Iterator over several tables returns besides points: the range
+ * keys in force at its snapshot (Iterator.RangeBounds / RangeKeys), and,
+ * optionally, the points that those range keys mask (IterOptions.RangeKeyMasking).
+ *
+ * A range-key RUN is what pbl_keyspan_decode with `extra` produces from one
+ * block: a decoded batch with ONE block, key = start, value = end, trailer kind
+ * in {RANGEKEYSET 21, RANGEKEYUNSET 20, RANGEKEYDEL 19}, and per KV the
+ * keyspan.Key's suffix and value in a pbl_keyspan_extra.  It is FRAGMENTED as
+ * the runs of range deletions are (above), trailers descending inside a span.
+ *
+ * The rules (rangekey.CoalesceInto, internal/rangekey/coalesce.go:64-151;
+ * UserIteratorConfig.Transform / ShouldDefragment,
+ * internal/rangekeystack/user_iterator.go:148-241; keyspanimpl.MergingIter;
+ * rangeKeyMasking.SpanChanged / SkipPoint, range_keys.go:259-362):
+ *  merge     the runs are fragmented at every boundary of any run; an elementary
+ *            interval holds the keys of every fragment that contains it, by
+ *            trailer descending, ties by (run, index in the run);
+ *  coalesce  a key is visible iff seq < snapshot (PBL_SEQNUM_MAX sees all); the
+ *            visible keys whose trailer is greater than the largest visible
+ *            RANGEKEYDEL trailer count (so at one sequence number a SET or UNSET
+ *            is not cut by a DEL, kinds being 21 > 20 > 19); among those, keys
+ *            whose suffixes compare equal under CompareRangeSuffixes
+ *            (pbl_range_suffix_compare) are one group and its first key wins; a
+ *            winner survives iff it is a SET; survivors by suffix ascending;
+ *  defragment  two abutting intervals join when they hold the same non-zero
+ *            number of survivors, suffixes pairwise compare-equal, values
+ *            pairwise byte-equal; a joined span keeps the keys (suffix bytes,
+ *            value bytes, trailers) of its leftmost interval; an interval
+ *            without survivors is no span and breaks a chain;
+ *  bounds    for [lower, upper) the spans that intersect it, the first one's
+ *            start raised to lower, the last one's end lowered to upper;
+ *  masking   with threshold suffix t: in the span covering a point k (start <=
+ *            k < end) the mask is the smallest suffix r among the keys with a
+ *            non-empty suffix and cmp(r, t) >= 0; k is masked iff its own suffix
+ *            (k[split(k):]) is non-empty and cmp(r, p) < 0.  A masked KV is
+ *            invisible everywhere, as a range-deleted one is.
+ *
+ * The SET is a decoded batch with ONE block and a pbl_keyspan_extra: one KV per
+ * (span, surviving set), spans ascending, a span's KVs in suffix order.  Per KV:
+ * key = the span's start, value = its end (among boundaries that compare equal
+ * the bytes of the first in (run, fragment index, start before end) order),
+ * trailer = the surviving set's, kv_flags 0, entry_off = the span's ordinal in
+ * its block; extra: the key's suffix and value, and span[kv] = the index in the
+ * block of the span's FIRST KV, which is how the mask reaches a span's keys with
+ * one load (the ordinal is in entry_off already).  blk_status[0], the set being
+ * empty on any of them, in order of precedence: the first run block status that
+ * is not PBL_OK; a kind outside {19, 20, 21} or PBL_KV_INVALID_KEY:
+ * PBL_UNSUPPORTED; a run that is not fragmented or holds another number of KVs
+ * than n_kv[r]: PBL_INVALID_ARG.  4 GiB or more of key, end, suffix or value
+ * bytes: PBL_UNSUPPORTED.  Sizes: an interval holds at most M = the sum over
+ * the runs of a run's longest span (in keys) survivors and there are at most
+ * 2T - 1 intervals (T = the runs' KVs), so at most (2T - 1) * M KVs come out,
+ * each with a start, an end, a suffix and a value no longer than the longest of
+ * the runs.  That bound is quadratic, so a caller offers what it expects; a
+ * smaller capacity (extra's included) writes the sizes (totals, blk_*_base,
+ * blk_suffix_base, blk_value_base), no bytes, and PBL_OVERFLOW in
+ * totals.status_mask, and the caller calls again with those sizes.
+ *
+ * pbl_rangekey_set_host builds the set over HOST arrays in the reference's
+ * sequential shape: it sorts the boundaries (std::stable_sort, unique), per
+ * interval gathers the keys with one cursor per run (the merging iterator's
+ * walk), sorts them by trailer, runs CoalesceInto and Transform literally, and
+ * defragments in one left-to-right walk.  The set is small next to a batch: a caller builds it
+ * once per read and copies it to the device for pbl_rangekey_mask (a device
+ * builder is not built).
+ *
+ * pbl_rangekey_clip_host: a decoded batch (HOST) with one block per range of
+ * `ranges` (HOST arrays; lower / upper keys, PBL_SCAN_NO_UPPER, n and comparer
+ * are read; an empty lower key is below every key), holding the set's spans
+ * that intersect the range, truncated to it, in the set's form with span[] and
+ * entry_off relative to the block.  Every block has the set's status.
+ * to_host(), the host iterator and the per-block seeks read it unchanged.
+ *
+ * pbl_rangekey_mask: THE HOT PATH.  For every KV of `batch` (n_blocks blocks,
+ * n_kv = its totals.n_kv as the host read it) that the masking rule hides under
+ * the set (DEVICE arrays) and the threshold mask_suffix (DEVICE, readable 16 B
+ * past its end; length 0 = the empty suffix, below every other), it stores
+ * PBL_RANGEDEL_ALL into cover_seq[kv] (DEVICE [n_kv]).  Every other entry is
+ * left as it is, so a cover from pbl_rangedel_cover composes with it (zero the
+ * array first when there is none), and the _rd view applies the masking.  KVs
+ * of blocks that are not PBL_OK are untouched; so is every KV when the set is
+ * empty, not PBL_OK or overflowed.  One launch, no workspace, stream-ordered,
+ * no host synchronisation.  The set's key, value and suffix bytes must be
+ * readable 16 B past their end, as for every source.
+ *
+ * pbl_rangekey_mask_set_host is the same lookup over HOST arrays.
+ * pbl_rangekey_mask_host takes the RUNS, not the set: per KV it gathers the
+ * keys of every fragment that covers it, coalesces them and applies
+ * SpanChanged / SkipPoint, so it checks the set builder and the lookup
+ * together; *status (optional) receives the status the set would have (nothing
+ * is stored with a status).
+ *
+ * PBL_INVALID_ARG, before anything else: NULL runs / set / extra / batch /
+ * cover_seq / ranges or a needed array, more than PBL_RANGEDEL_MAX_RUNS runs,
+ * runs->runs, runs->extras or runs->n_kv NULL with n_runs > 0, comparer >
+ * PBL_CMP_CRDB, 2^31 fragments or more, mask_suffix NULL with a length.
+ */
+#define PBL_KIND_RANGEKEYDEL 19u   /* InternalKeyKindRangeKeyDelete (internal/base/internal.go:29-130) */
+#define PBL_KIND_RANGEKEYUNSET 20u /* InternalKeyKindRangeKeyUnset */
+#define PBL_KIND_RANGEKEYSET 21u   /* InternalKeyKindRangeKeySet   */
+
+typedef struct pbl_rangekey_runs {
+  const pbl_decode_out* runs;      /* HOST array [n_runs]; one block each; the arrays each names are DEVICE
+                                      (HOST for the host forms); capacities and workspace fields unused */
+  const pbl_keyspan_extra* extras; /* HOST array [n_runs]: each run's suffixes and values */
+  const uint64_t* n_kv;            /* HOST [n_runs]: each run's totals.n_kv as the host read it */
+  uint32_t n_runs, comparer /* PBL_CMP_* */;
+  uint64_t snapshot;
+} pbl_rangekey_runs;
+
+/* Comparer.CompareRangeSuffixes: bytes.Compare (default), testkeys'
+ * compareSuffixes, cockroachkvs.CompareRangeSuffixes: -1 / 0 / +1. */
+int pbl_range_suffix_compare(uint32_t comparer, const uint8_t* a, uint64_t a_len, const uint8_t* b, uint64_t b_len);
+int pbl_rangekey_set_host(const pbl_rangekey_runs* runs, pbl_decode_out* set, pbl_keyspan_extra* set_extra);
+int pbl_rangekey_clip_host(const pbl_decode_out* set, const pbl_keyspan_extra* set_extra, const pbl_scan_queries* ranges,
+                           pbl_decode_out* out, pbl_keyspan_extra* out_extra);
+int pbl_rangekey_mask(const pbl_decode_out* set, const pbl_keyspan_extra* set_extra, const pbl_decode_out* batch,
+                      uint32_t n_blocks, uint64_t n_kv, uint32_t comparer, const uint8_t* mask_suffix,
+                      uint64_t mask_suffix_len, uint64_t* cover_seq, void* stream);
+int pbl_rangekey_mask_set_host(const pbl_decode_out* set, const pbl_keyspan_extra* set_extra,
+                               const pbl_decode_out* batch, uint32_t n_blocks, uint32_t comparer,
+                               const uint8_t* mask_suffix, uint64_t mask_suffix_len, uint64_t* cover_seq);
+int pbl_rangekey_mask_host(const pbl_rangekey_runs* runs, const pbl_decode_out* batch, uint32_t n_blocks,
+                           const uint8_t* mask_suffix, uint64_t mask_suffix_len, uint64_t* cover_seq,
+                           uint32_t* status);
+/* sizeof(pbl_rangekey_runs), its 6 field offsets (the other layout lists are
+ * unchanged; ABI version 9 stands). */
+size_t pbl_rangekey_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,16 @@ class KeyspanExtraC(ctypes.Structure):  # pbl_keyspan_extra
                 ("value_cap", ctypes.c_uint64)]
 
 
+# range keys in the read path (pbl_rangekey_set_host, pbl_rangekey_mask)
+PBL_KIND_RANGEKEYDEL, PBL_KIND_RANGEKEYUNSET, PBL_KIND_RANGEKEYSET = 19, 20, 21
+
+
+class RangekeyRunsC(ctypes.Structure):  # pbl_rangekey_runs
+    _fields_ = [("runs", ctypes.POINTER(DecodeOutC)), ("extras", ctypes.POINTER(KeyspanExtraC)),
+                ("n_kv", ctypes.POINTER(ctypes.c_uint64)), ("n_runs", ctypes.c_uint32), ("comparer", ctypes.c_uint32),
+                ("snapshot", ctypes.c_uint64)]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -347,6 +357,22 @@ SIGNATURES = {
     "pbl_keyspan_decode_host": (ctypes.c_int, [ctypes.POINTER(BlockBatchC), ctypes.POINTER(DecodeOutC),
                                                ctypes.POINTER(KeyspanExtraC)]),
     "pbl_keyspan_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_range_suffix_compare": (ctypes.c_int, [ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, ctypes.c_uint64]),
+    "pbl_rangekey_set_host": (ctypes.c_int, [ctypes.POINTER(RangekeyRunsC), ctypes.POINTER(DecodeOutC),
+                                             ctypes.POINTER(KeyspanExtraC)]),
+    "pbl_rangekey_clip_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.POINTER(KeyspanExtraC),
+                                              ctypes.POINTER(ScanQueriesC), ctypes.POINTER(DecodeOutC),
+                                              ctypes.POINTER(KeyspanExtraC)]),
+    "pbl_rangekey_mask": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.POINTER(KeyspanExtraC),
+                                         ctypes.POINTER(DecodeOutC), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                         _vp, ctypes.c_uint64, _vp, _vp]),
+    "pbl_rangekey_mask_set_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.POINTER(KeyspanExtraC),
+                                                  ctypes.POINTER(DecodeOutC), ctypes.c_uint32, ctypes.c_uint32, _u8p,
+                                                  ctypes.c_uint64, _vp]),
+    "pbl_rangekey_mask_host": (ctypes.c_int, [ctypes.POINTER(RangekeyRunsC), ctypes.POINTER(DecodeOutC),
+                                              ctypes.c_uint32, _u8p, ctypes.c_uint64, _vp,
+                                              ctypes.POINTER(ctypes.c_uint32)]),
+    "pbl_rangekey_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

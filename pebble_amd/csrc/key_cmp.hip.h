@@ -133,6 +133,32 @@ PBL_HD inline int key_cmp(uint32_t cmp, kptr<R> a, uint64_t al, kptr<R> b, uint6
     default: return R::bytes_cmp(a, al, b, bl);
   }
 }
+// Comparer.CompareRangeSuffixes: the order of range-key suffixes (DESIGN.md
+// §3.16).  It is not key_cmp's suffix step: bytes.Compare for the default
+// comparer (internal/base/comparer.go:317); testkeys' compareSuffixes
+// (testkeys.go:173-186), which orders two equal timestamps by the "_synthetic"
+// mark (the unmarked one first); cockroachkvs.CompareRangeSuffixes
+// (cockroachkvs.go:346-355), the versions without their length byte, descending
+// and NOT normalised.  Malformed testkeys suffixes sort by bytes, as in tk_cmp.
+template <class R>
+PBL_HD inline int suffix_cmp(uint32_t cmp, kptr<R> a, uint64_t al, kptr<R> b, uint64_t bl) {
+  switch (cmp) {
+    case PBL_CMP_TESTKEYS: {
+      const uint64_t at = tk_trim<R>(a, al), bt = tk_trim<R>(b, bl);
+      int c;
+      uint64_t x, y;
+      if (at == 0 || bt == 0) c = at < bt ? -1 : at > bt ? 1 : 0;
+      else if (!tk_ts<R>(a, at, &x) || !tk_ts<R>(b, bt, &y)) c = R::bytes_cmp(a, at, b, bt);
+      else c = y < x ? -1 : y > x ? 1 : 0;
+      if (c == 0 && (at != al) != (bt != bl)) c = at != al ? 1 : -1;
+      return c;
+    }
+    case PBL_CMP_CRDB:
+      if (al == 0 || bl == 0) return al < bl ? -1 : al > bl ? 1 : 0;
+      return R::bytes_cmp(b, bl - 1, a, al - 1);
+    default: return R::bytes_cmp(a, al, b, bl);
+  }
+}
 // base.InternalCompare (internal/base/internal.go:431-437), which is also
 // mergingIterHeap.less (merging_iter_heap.go:55-67): the user keys under the
 // comparer, then the trailers in reverse (the newer version sorts first).

@@ -52,6 +52,7 @@ KEY_SCHEMA_PROP = b"pebble.colblk.schema"
 PROPERTIES_NAME = b"rocksdb.properties"
 VALUE_INDEX_NAME = b"pebble.value_index"
 RANGE_DEL_NAME = b"rocksdb.range_del2"  # table.go metaRangeDelV2Name
+RANGE_KEY_NAME = b"pebble.range_key"    # table.go metaRangeKeyName (sstable/table.go:229)
 COMPARER_PROP = b"rocksdb.comparator"
 COMPARERS = {b"leveldb.BytewiseComparator": N.PBL_CMP_DEFAULT, b"pebble.internal.testkeys": N.PBL_CMP_TESTKEYS,
              b"cockroach_comparator": N.PBL_CMP_CRDB}
@@ -431,6 +432,27 @@ class Table:
         d = decode(self._handle_blocks([h], N.PBL_FMT_ROW))
         if d.read_totals().status_mask:
             raise DecodeError("range-del block corrupt")
+        return d
+
+    def range_keys(self):
+        """The table's range-key fragments as a range-key run
+        (`pebble_amd.rangekey`): the metaindex's "pebble.range_key" block through
+        the physical step and `keyspan.decode(extras=True)` (a `keyspan.Decoded`:
+        key = start, value = end, and per KV the suffix and the value), or None
+        when the table has none.  A row-format table packs end key, suffixes and
+        values into the value (internal/rangekey/rangekey.go); that form is not
+        decoded here."""
+        h = self.metaindex().get(RANGE_KEY_NAME)
+        if h is None:
+            return None
+        if not self.footer.columnar:
+            raise DecodeError("row-format range-key blocks are out of scope: only columnar tables' "
+                              "pebble.range_key blocks are read")
+        from .keyspan import decode as keyspan_decode
+        d = keyspan_decode(self._handle_blocks([h], N.PBL_FMT_ROW), extras=True)
+        if d.batch.read_totals().status_mask:
+            raise DecodeError("range-key keyspan block corrupt "
+                              f"({N.STATUS_NAMES.get(int(d.batch.blk_status[0].item()), '?')})")
         return d
 
     # -- positioning: batched seeks over the decoded table (pebble_amd.seek) --------

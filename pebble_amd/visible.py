@@ -144,7 +144,7 @@ def visible_host(host: dict, *, comparer: int, snapshot: int = SEQNUM_MAX, keep_
 
 def read(tables, lowers: Sequence[Optional[bytes]], uppers: Sequence[Optional[bytes]], *, snapshot: int = SEQNUM_MAX,
          hide_obsolete_points: bool = False, keep_operands: bool = False, range_dels=None, levels=None,
-         range_del_levels=None) -> VisibleResult:
+         range_del_levels=None, range_keys=None, with_range_keys: bool = False, mask_suffix: Optional[bytes] = None):
     """`merge_scan` of the tables over the ranges, then `visible`: per range
     what an Iterator with those bounds over the tables returns going forward
     (point keys; src_kv indexes the merge result).  Range deletions apply:
@@ -156,7 +156,19 @@ def read(tables, lowers: Sequence[Optional[bytes]], uppers: Sequence[Optional[by
     level, as the reference does: a tombstone of a shallower level deletes
     whatever the sequence numbers are.  It matters only where sequence numbers
     are not ordered by level; without it the rule is the sequence-number one.
-    Caller-supplied runs then need `range_del_levels`, one per run."""
+    Caller-supplied runs then need `range_del_levels`, one per run.
+
+    Range keys (`pebble_amd.rangekey`): `range_keys` is a list of range-key runs
+    (`keyspan.Decoded`), by default the tables' own (`Table.range_keys()`).  With
+    `with_range_keys` the result is `(points, range_key_batch)`, the second being
+    the coalesced, defragmented set at the snapshot truncated to the same ranges
+    (`rangekey.clip_host`, on the device as a `keyspan.Decoded` with one block
+    per range): what Iterator.RangeBounds / RangeKeys report.  With `mask_suffix`
+    (IterOptions.RangeKeyMasking.Suffix) the points that the set masks are
+    hidden: `rangekey.mask` stores them into the cover before the view.  The set
+    is built by the host form (small next to the batch) and copied over; the
+    mask runs on the device.  With none of the three the call path and the
+    result are the ones without range keys."""
     tables = list(tables)
     comparer = tables[0].comparer()
     merged = merge_scan(tables, lowers, uppers, hide_obsolete_points=hide_obsolete_points)
@@ -180,4 +192,21 @@ def read(tables, lowers: Sequence[Optional[bytes]], uppers: Sequence[Optional[by
                                                               if mask >> b & 1))
         cover = rangedel.cover(rset, merged.batch, comparer, src_run=merged.src_run if levels is not None else None,
                                run_levels=levels)
-    return visible(merged.batch, comparer=comparer, snapshot=snapshot, keep_operands=keep_operands, cover=cover)
+    rk_batch = None
+    if range_keys is not None or with_range_keys or mask_suffix is not None:
+        from . import rangekey
+        if range_keys is None:
+            own_rk = [t.range_keys() for t in tables if hasattr(t, "range_keys")]
+            range_keys = [r for r in own_rk if r is not None]
+        hosts = [r.to_host() for r in range_keys]
+        rk_set = rangekey.build_set_host(hosts, comparer, snapshot)
+        if rk_set["status_mask"]:
+            raise DecodeError("range keys: " + ", ".join(N.STATUS_NAMES.get(b, str(b)) for b in range(32)
+                                                         if rk_set["status_mask"] >> b & 1))
+        dev = merged.batch.trailer.device
+        if with_range_keys:
+            rk_batch = rangekey.to_device(rangekey.clip_host(rk_set, lowers, uppers, comparer), dev)
+        if mask_suffix is not None and rk_set["n_kv"]:
+            cover = rangekey.mask(rangekey.to_device(rk_set, dev), merged.batch, comparer, mask_suffix, cover=cover)
+    points = visible(merged.batch, comparer=comparer, snapshot=snapshot, keep_operands=keep_operands, cover=cover)
+    return (points, rk_batch) if with_range_keys else points
