@@ -1435,7 +1435,8 @@ size_t pbl_keyspan_struct_layout(uint64_t* out, size_t cap);
  * `ranges` (HOST arrays; lower / upper keys, PBL_SCAN_NO_UPPER, n and comparer
  * are read; an empty lower key is below every key), holding the set's spans
  * that intersect the range, truncated to it, in the set's form with span[] and
- * entry_off relative to the block.  Every block has the set's status.
+ * entry_off relative to the block.  An empty or inverted range (upper <= lower)
+ * intersects nothing: its block is empty.  Every block has the set's status.
  * to_host(), the host iterator and the per-block seeks read it unchanged.
  *
  * pbl_rangekey_mask: THE HOT PATH.  For every KV of `batch` (n_blocks blocks,

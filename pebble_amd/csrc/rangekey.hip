@@ -487,6 +487,8 @@ int pbl_rangekey_clip_host(const pbl_decode_out* set, const pbl_keyspan_extra* s
       M::HSpan t = s;
       if (pbl::cmp::key_cmp<R>(c, t.s.k, t.s.kl, lo.k, lo.kl) < 0) t.s = lo;
       if (!no_upper && pbl::cmp::key_cmp<R>(c, hi.k, hi.kl, t.e.k, t.e.kl) < 0) t.e = hi;
+      // an empty or inverted range (upper <= lower) intersects nothing: no empty or inverted span
+      if (pbl::cmp::key_cmp<R>(c, t.s.k, t.s.kl, t.e.k, t.e.kl) >= 0) continue;
       spans.push_back(std::move(t));
     }
     first.push_back(spans.size());

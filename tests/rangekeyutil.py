@@ -167,6 +167,8 @@ def clip_spans(spans, lower, upper, comparer):
             s = lower
         if upper is not None and key_compare(comparer, upper, e) < 0:
             e = upper
+        if key_compare(comparer, s, e) >= 0:  # (an empty or inverted range intersects nothing)
+            continue
         out.append((s, e, ks))
     return out
 
