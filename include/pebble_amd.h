@@ -63,8 +63,10 @@ enum {
   PBL_CORRUPT_COMPRESSION = 11,  /* snappy.ErrCorrupt -> base.MarkCorruptionError (block.go:550-565) */
   PBL_CORRUPT_FOOTER = 12,       /* parseFooter's CorruptionErrorf sites (sstable/table.go:328-404) */
   PBL_CORRUPT_INDEX = 13,        /* DecodeHandleWithProperties "invalid block.Handle" (block/block.go:94-104) */
-  PBL_CORRUPT_VALUE_HANDLE = 14  /* valblk handle/index entry out of bounds (valblk/valblk.go:370-393,
+  PBL_CORRUPT_VALUE_HANDLE = 14, /* valblk handle/index entry out of bounds (valblk/valblk.go:370-393,
                                     valblk/reader.go:280-302) */
+  PBL_CORRUPT_FILTER = 15        /* a bloom filter block whose trailer does not match its length
+                                    (tablefilters/bloom/bits.go:100-102 panics there) */
 };
 
 /* ---- block formats ---------------------------------------------------------- */
@@ -1494,6 +1496,100 @@ int pbl_rangekey_mask_host(const pbl_rangekey_runs* runs, const pbl_decode_out* 
 /* sizeof(pbl_rangekey_runs), its 6 field offsets (the other layout lists are
  * unchanged; ABI version 9 stands). */
 size_t pbl_rangekey_struct_layout(uint64_t* out, size_t cap);
+
+/* ---- table bloom filters: batched probes and SeekPrefixGE ----
+ * The filter block of a table ("fullfilter.rocksdb.BuiltinBloomFilter" in the
+ * metaindex; sstable/tablefilters/bloom): nLines * 64 bytes of bits, one byte
+ * of probes, LE32 nLines -- the RocksDB full-file format.  The rules are
+ * filter_core.hip.h's, stated once for host and device:
+ *
+ *   hash   bloom.go:41-78 over key[:Split(key)] under `comparer` (what a table's
+ *          writer adds, and what Get / SeekPrefixGE ask for)
+ *   parse  bits.go:93-105.  A filter of 5 bytes or fewer holds nothing: every
+ *          probe answers "no", status PBL_OK.  nLines == 0, or a length that is
+ *          not the one nLines gives (8 * ((len - 5) / nLines) != 512), is
+ *          PBL_CORRUPT_FILTER (the reference panics).
+ *   probe  bits.go:39-53: line h % nLines, nProbes bits of it, h += rotr(h, 17)
+ *          between them.  nProbes is what the byte says (0 .. 255); zero probes
+ *          answer "yes".
+ *
+ * pbl_filter_probe: one launch, a lane per key.  Named mode (q->filter != NULL):
+ * key i against filter q->filter[i], may[i].  All-pairs mode (q->filter == NULL):
+ * every key against every filter, hashed once, may[f * n + i].  may bits:
+ * PBL_FILTER_MAY is the reference's MayContain; PBL_FILTER_BAD marks a filter id
+ * >= n_filters or a corrupt filter, and then PBL_FILTER_MAY is set too: a caller
+ * that ignores statuses must never lose a key (the entry points are
+ * asynchronous: it cannot be a return code).  hash[i] (optional) is the hash of
+ * key i's prefix; flt_status[f] (optional) the parse status of filter f.
+ * off[] must be non-decreasing; filter f is bytes[off[f] .. off[f + 1]).
+ *
+ * PBL_INVALID_ARG, before any device call: a NULL struct, NULL may, NULL
+ * key_off, comparer > PBL_CMP_CRDB.  n == 0 or n_filters == 0 returns PBL_OK
+ * without a launch.
+ *
+ * pbl_filter_probe_host is the same over HOST pointers (single-threaded, no
+ * device call, nothing read past a key's end).
+ *
+ * pbl_bloom_build_host is the writer (bloom.go:100-123, bits.go:73-89): the
+ * hash of every key's Split-prefix in the order given, a hash equal to the one
+ * before it dropped (hash_collector.go:39-42), nLines = ((numHashes *
+ * bits_per_key + 511) / 512) | 1, the probe count of bloom.go:23-34.  Zero
+ * hashes give *out_len = 0.  PBL_OVERFLOW (and the needed *out_len) when `cap`
+ * is less than the filter; pbl_bloom_build_bound(n, bits_per_key) is always
+ * enough.  bits_per_key == 0 is PBL_INVALID_ARG (FilterPolicy panics).  It
+ * exists to make inputs and has no device form.
+ */
+#define PBL_FILTER_MAY 0x1u
+#define PBL_FILTER_BAD 0x2u
+
+typedef struct pbl_filter_set {      /* F filters, concatenated in one device buffer */
+  const uint8_t*  bytes;             /* DEVICE */
+  const uint64_t* off;               /* DEVICE [n_filters + 1] */
+  uint32_t n_filters;
+} pbl_filter_set;
+
+typedef struct pbl_filter_queries {
+  const uint8_t*  key_bytes;         /* DEVICE, readable 16 B past the last key */
+  const uint64_t* key_off;           /* DEVICE [n + 1] */
+  const uint32_t* filter;            /* DEVICE [n] one filter id per key, or NULL: every key against every filter */
+  uint32_t n, comparer;              /* the probed bytes are key[:Split(key)] */
+} pbl_filter_queries;
+
+typedef struct pbl_filter_out {
+  uint8_t*  may;        /* DEVICE [n] (named mode) or [n_filters * n], filter-major (all-pairs mode) */
+  uint32_t* hash;       /* DEVICE [n], optional: bloom_hash of every key's prefix */
+  int32_t*  flt_status; /* DEVICE [n_filters], optional: PBL_OK / PBL_CORRUPT_FILTER */
+} pbl_filter_out;
+
+int pbl_filter_probe(const pbl_filter_set* set, const pbl_filter_queries* q, pbl_filter_out* out, void* stream);
+int pbl_filter_probe_host(const pbl_filter_set* set, const pbl_filter_queries* q, pbl_filter_out* out);
+int pbl_bloom_build_host(const uint8_t* key_bytes, const uint64_t* key_off, uint64_t n, uint32_t comparer,
+                         uint32_t bits_per_key, uint8_t* out, uint64_t cap, uint64_t* out_len);
+uint64_t pbl_bloom_build_bound(uint64_t n, uint32_t bits_per_key);
+/* sizeof(pbl_filter_set), its 3 field offsets, sizeof(pbl_filter_queries), its 5,
+ * sizeof(pbl_filter_out), its 3 (the other layout lists are unchanged; ABI
+ * version 9 stands: the additions change no existing struct or function). */
+size_t pbl_filter_struct_layout(uint64_t* out, size_t cap);
+
+/* singleLevelIterator.SeekPrefixGE with useFilterBlock
+ * (sstable/reader_iter_single_lvl.go:1037-1107) in one launch: the prefix is the
+ * query's own Split-prefix; a query whose prefix the filter excludes gets
+ * PBL_SEEK_NONE, block 0 and flags PBL_SEEK_FILTERED, and its lane does no
+ * search; every other query gets exactly what pbl_seek_batch gives it.  The
+ * search is pbl_seek_batch's (seek_core.hip.h seek_one) behind that one
+ * predicate.  `filter` is one filter block as above.  A corrupt filter excludes
+ * nothing, and every answered query also carries PBL_SEEK_BAD_BLOCK.  Only
+ * table mode (q->block == NULL) with PBL_SEEK_GE: anything else, or a NULL
+ * filter, is PBL_INVALID_ARG, as is whatever pbl_seek_batch refuses.  A
+ * synthetic prefix (bloomFilterMayContain, :1117-1126) is the caller's to strip.
+ */
+#define PBL_SEEK_FILTERED 0x8u   /* the table's filter excluded the key's prefix: kv = PBL_SEEK_NONE, no search ran */
+
+int pbl_seek_prefix_batch(const pbl_decode_out* decoded, uint32_t n_blocks, const pbl_seek_queries* q,
+                          const uint8_t* filter /* DEVICE */, uint64_t filter_len,
+                          pbl_seek_out* out, const void* workspace, uint64_t workspace_bytes, void* stream);
+int pbl_seek_prefix_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl_seek_queries* q,
+                               const uint8_t* filter, uint64_t filter_len, pbl_seek_out* out);
 
 #ifdef __cplusplus
 }

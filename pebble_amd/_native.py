@@ -29,11 +29,13 @@ PBL_CORRUPT_COMPRESSION = 11
 PBL_CORRUPT_FOOTER = 12
 PBL_CORRUPT_INDEX = 13
 PBL_CORRUPT_VALUE_HANDLE = 14
+PBL_CORRUPT_FILTER = 15
 STATUS_NAMES = {
     0: "OK", 1: "CORRUPT_NO_RESTARTS", 2: "CORRUPT_FIRST_KEY", 3: "CORRUPT_BOUNDS",
     4: "CORRUPT_COLBLK_HEADER", 5: "UNSUPPORTED", 6: "OVERFLOW", 7: "INVALID_ARG",
     8: "DEVICE_ERROR", 9: "TIMEOUT", 10: "CORRUPT_CHECKSUM", 11: "CORRUPT_COMPRESSION",
     12: "CORRUPT_FOOTER", 13: "CORRUPT_INDEX", 14: "CORRUPT_VALUE_HANDLE",
+    15: "CORRUPT_FILTER",
 }
 # TableFormat (footer magic, version)
 PBL_TABLE_LEVELDB, PBL_TABLE_ROCKSDBV2 = 1, 2
@@ -268,6 +270,24 @@ class RangekeyRunsC(ctypes.Structure):  # pbl_rangekey_runs
                 ("snapshot", ctypes.c_uint64)]
 
 
+# table bloom filters (pbl_filter_probe, pbl_seek_prefix_batch)
+PBL_FILTER_MAY, PBL_FILTER_BAD = 0x1, 0x2
+PBL_SEEK_FILTERED = 0x8
+
+
+class FilterSetC(ctypes.Structure):  # pbl_filter_set
+    _fields_ = [("bytes", _vp), ("off", _vp), ("n_filters", ctypes.c_uint32)]
+
+
+class FilterQueriesC(ctypes.Structure):  # pbl_filter_queries
+    _fields_ = [("key_bytes", _vp), ("key_off", _vp), ("filter", _vp), ("n", ctypes.c_uint32),
+                ("comparer", ctypes.c_uint32)]
+
+
+class FilterOutC(ctypes.Structure):  # pbl_filter_out
+    _fields_ = [("may", _vp), ("hash", _vp), ("flt_status", _vp)]
+
+
 # Every symbol include/pebble_amd.h declares, with its ctypes signature.
 SIGNATURES = {
     "pbl_data_iter_new": (_vp, []),
@@ -373,6 +393,20 @@ SIGNATURES = {
                                               ctypes.c_uint32, _u8p, ctypes.c_uint64, _vp,
                                               ctypes.POINTER(ctypes.c_uint32)]),
     "pbl_rangekey_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_filter_probe": (ctypes.c_int, [ctypes.POINTER(FilterSetC), ctypes.POINTER(FilterQueriesC),
+                                        ctypes.POINTER(FilterOutC), _vp]),
+    "pbl_filter_probe_host": (ctypes.c_int, [ctypes.POINTER(FilterSetC), ctypes.POINTER(FilterQueriesC),
+                                             ctypes.POINTER(FilterOutC)]),
+    "pbl_bloom_build_host": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                            ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "pbl_bloom_build_bound": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32]),
+    "pbl_filter_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_seek_prefix_batch": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
+                                             ctypes.POINTER(SeekQueriesC), _vp, ctypes.c_uint64,
+                                             ctypes.POINTER(SeekOutC), _vp, ctypes.c_uint64, _vp]),
+    "pbl_seek_prefix_batch_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
+                                                  ctypes.POINTER(SeekQueriesC), _vp, ctypes.c_uint64,
+                                                  ctypes.POINTER(SeekOutC)]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

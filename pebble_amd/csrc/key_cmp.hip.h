@@ -44,6 +44,11 @@ struct HostReader {
     *w0 = w[0];
     *w1 = w[1];
   }
+  // the first min(n, 16) bytes as four little-endian words, zero padded
+  static void load_le16(const uint8_t* a, uint64_t n, uint32_t w[4]) {
+    w[0] = w[1] = w[2] = w[3] = 0;
+    for (uint64_t i = 0; i < n && i < 16; i++) w[i >> 2] |= uint32_t(a[i]) << (8 * (i & 3));
+  }
 };
 
 template <class R>

@@ -18,6 +18,12 @@
 //       both records hold, else by the full compare), binary search inside
 //       the block, the HideObsoletePoints skip, the flags, three plain stores
 //
+//   seek_kernel<comparer, true>  (pbl_seek_prefix_batch) SeekPrefixGE with
+//       useFilterBlock (reader_iter_single_lvl.go:1037-1107): the same kernel
+//       behind one more predicate, the table's bloom filter asked for the
+//       query's Split-prefix (filter_core.hip.h); an excluded query's lane does
+//       no search
+//
 // seek_one<R> (seek_core.hip.h, shared with scan.hip) is the whole search; the
 // kernel instantiates it with GlobalReader and pbl_seek_batch_host with
 // cmp::HostReader.  The comparers are key_cmp.hip.h's; GlobalReader specialises
@@ -25,6 +31,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "filter_core.hip.h"
 #include "seek_core.hip.h"
 
 namespace pbl {
@@ -41,7 +48,24 @@ struct SeekArgs {
   pbl_seek_out out;
   uint32_t n_blocks;
   const uint8_t* ws;
+  const uint8_t* filter;  // pbl_seek_prefix_batch only
+  uint64_t filter_len;
 };
+
+// What SeekPrefixGE asks the filter before it searches: 0 to go on, else the
+// flags of the answer -- PBL_SEEK_FILTERED when the filter excludes the query's
+// Split-prefix (no search), PBL_SEEK_BAD_BLOCK for a corrupt filter, which
+// excludes nothing.
+template <class R, uint32_t kCmp>
+PBL_HD inline uint8_t filter_gate(typename R::template ptr<const uint8_t> filter, uint64_t filter_len,
+                                  typename R::template ptr<const uint8_t> q_bytes,
+                                  typename R::template ptr<const uint64_t> q_off, uint64_t i) {
+  const filter::Header H = filter::bloom_parse<R>(filter, filter_len);
+  if (H.status != PBL_OK) return PBL_SEEK_BAD_BLOCK;
+  const uint64_t q0 = q_off[i];
+  const uint32_t h = filter::prefix_hash<R>(kCmp, q_bytes + q0, q_off[i + 1] - q0);
+  return filter::bloom_may<R>(filter, H, h) ? 0 : PBL_SEEK_FILTERED;
+}
 
 __device__ inline View<GlobalReader> fence_view(const FenceArgs& A) {
   pbl_seek_queries q{};
@@ -110,10 +134,21 @@ __global__ __launch_bounds__(kSeekTPB) void seek_fence_kernel(FenceArgs A) {
   }
 }
 
-template <uint32_t kCmp>
+template <uint32_t kCmp, bool kFilter>
 __global__ __launch_bounds__(kSeekTPB) void seek_kernel(SeekArgs A) {
   const uint64_t i = uint64_t(blockIdx.x) * kSeekTPB + threadIdx.x;
   if (i >= A.q.n) return;
+  uint8_t gate = 0;
+  if (kFilter) {
+    gate = filter_gate<GlobalReader, kCmp>(to_glb(A.filter), A.filter_len, to_glb(A.q.key_bytes),
+                                           to_glb(A.q.key_off), i);
+    if (gate & PBL_SEEK_FILTERED) {
+      to_glb(A.out.kv)[i] = PBL_SEEK_NONE;
+      if (A.out.block) to_glb(A.out.block)[i] = 0u;
+      if (A.out.flags) to_glb(A.out.flags)[i] = gate;
+      return;
+    }
+  }
   uint32_t nf = 0;
   bool stale = false;
   if (!A.q.block) {
@@ -130,7 +165,7 @@ __global__ __launch_bounds__(kSeekTPB) void seek_kernel(SeekArgs A) {
   }
   to_glb(A.out.kv)[i] = L.kv;
   if (A.out.block) to_glb(A.out.block)[i] = L.block;
-  if (A.out.flags) to_glb(A.out.flags)[i] = L.flags;
+  if (A.out.flags) to_glb(A.out.flags)[i] = L.flags | gate;
 }
 
 
@@ -142,6 +177,60 @@ inline bool args_ok(const pbl_decode_out* d, const pbl_seek_queries* q, const pb
   if (!d->blk_status || !d->blk_kv_base || !d->blk_key_base || !d->key_off || !d->key_bytes) return false;
   if (q->hide_obsolete_points && !d->kv_flags) return false;
   return true;
+}
+// pbl_seek_prefix_batch: table mode, SeekGE, a filter block.
+inline bool prefix_args_ok(const pbl_decode_out* d, const pbl_seek_queries* q, const uint8_t* filter,
+                           const pbl_seek_out* out) {
+  return args_ok(d, q, out) && filter && !q->block && q->op == PBL_SEEK_GE;
+}
+
+template <bool kFilter>
+int launch_seek(const pbl_decode_out* decoded, uint32_t n_blocks, const pbl_seek_queries* q, const uint8_t* filter,
+                uint64_t filter_len, pbl_seek_out* out, const void* workspace, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  SeekArgs a;
+  a.d = *decoded;
+  a.q = *q;
+  a.out = *out;
+  a.n_blocks = n_blocks;
+  a.ws = static_cast<const uint8_t*>(workspace);
+  a.filter = filter;
+  a.filter_len = filter_len;
+  const uint32_t grid = uint32_t((uint64_t(q->n) + kSeekTPB - 1) / kSeekTPB);
+  with_cmp(q->comparer, [&](auto c) {
+    hipLaunchKernelGGL((seek_kernel<decltype(c)::value, kFilter>), dim3(grid), dim3(kSeekTPB), 0, st, a);
+    return 0;
+  });
+  return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
+}
+
+// The host form of both entry points (filter == NULL: pbl_seek_batch_host).
+inline int seek_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl_seek_queries* q, const uint8_t* filter,
+                     uint64_t filter_len, pbl_seek_out* out) {
+  using R = cmp::HostReader;
+  std::vector<Fence> fence;
+  if (!q->block) {  // what pbl_seek_prepare builds, by the same two functions
+    const View<R> V0(*host, n_blocks, *q, nullptr, 0);
+    for (uint32_t b = 0; b < n_blocks; b++)
+      if (listed(V0, b)) fence.push_back(fence_of<R>(q->comparer, V0, b));
+  }
+  const View<R> V(*host, n_blocks, *q, fence.data(), uint32_t(fence.size()));
+  with_cmp(q->comparer, [&](auto c) {
+    constexpr uint32_t kc = decltype(c)::value;
+    for (uint64_t i = 0; i < q->n; i++) {
+      const uint8_t gate = filter ? filter_gate<R, kc>(filter, filter_len, q->key_bytes, q->key_off, i) : uint8_t(0);
+      Landing L{PBL_SEEK_NONE, 0u, gate};
+      if (!(gate & PBL_SEEK_FILTERED)) {
+        L = seek_one<R, kc>(V, i);
+        L.flags |= gate;
+      }
+      out->kv[i] = L.kv;
+      if (out->block) out->block[i] = L.block;
+      if (out->flags) out->flags[i] = L.flags;
+    }
+    return 0;
+  });
+  return PBL_OK;
 }
 
 }  // namespace seek
@@ -180,43 +269,33 @@ int pbl_seek_batch(const pbl_decode_out* decoded, uint32_t n_blocks, const pbl_s
     return PBL_INVALID_ARG;
   if (!q->block && !workspace) return PBL_INVALID_ARG;
   if (q->n == 0) return PBL_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  S::SeekArgs a;
-  a.d = *decoded;
-  a.q = *q;
-  a.out = *out;
-  a.n_blocks = n_blocks;
-  a.ws = static_cast<const uint8_t*>(workspace);
-  const uint32_t grid = uint32_t((uint64_t(q->n) + S::kSeekTPB - 1) / S::kSeekTPB);
-  S::with_cmp(q->comparer, [&](auto c) {
-    hipLaunchKernelGGL(S::seek_kernel<decltype(c)::value>, dim3(grid), dim3(S::kSeekTPB), 0, st, a);
-    return 0;
-  });
-  return hipGetLastError() == hipSuccess ? PBL_OK : PBL_DEVICE_ERROR;
+  return S::launch_seek<false>(decoded, n_blocks, q, nullptr, 0, out, workspace, stream);
+}
+
+int pbl_seek_prefix_batch(const pbl_decode_out* decoded, uint32_t n_blocks, const pbl_seek_queries* q,
+                          const uint8_t* filter, uint64_t filter_len, pbl_seek_out* out, const void* workspace,
+                          uint64_t workspace_bytes, void* stream) {
+  namespace S = pbl::seek;
+  if (!S::prefix_args_ok(decoded, q, filter, out)) return PBL_INVALID_ARG;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < S::ws_size(n_blocks))
+    return PBL_INVALID_ARG;
+  if (q->n == 0) return PBL_OK;
+  return S::launch_seek<true>(decoded, n_blocks, q, filter, filter_len, out, workspace, stream);
+}
+
+int pbl_seek_prefix_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl_seek_queries* q,
+                               const uint8_t* filter, uint64_t filter_len, pbl_seek_out* out) {
+  namespace S = pbl::seek;
+  if (!S::prefix_args_ok(host, q, filter, out)) return PBL_INVALID_ARG;
+  if (q->n == 0) return PBL_OK;
+  return S::seek_host(host, n_blocks, q, filter, filter_len, out);
 }
 
 int pbl_seek_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl_seek_queries* q, pbl_seek_out* out) {
   namespace S = pbl::seek;
-  using R = pbl::cmp::HostReader;
   if (!S::args_ok(host, q, out)) return PBL_INVALID_ARG;
   if (q->n == 0) return PBL_OK;
-  std::vector<S::Fence> fence;
-  if (!q->block) {  // what pbl_seek_prepare builds, by the same two functions
-    const S::View<R> V0(*host, n_blocks, *q, nullptr, 0);
-    for (uint32_t b = 0; b < n_blocks; b++)
-      if (S::listed(V0, b)) fence.push_back(S::fence_of<R>(q->comparer, V0, b));
-  }
-  const S::View<R> V(*host, n_blocks, *q, fence.data(), uint32_t(fence.size()));
-  S::with_cmp(q->comparer, [&](auto c) {
-    for (uint64_t i = 0; i < q->n; i++) {
-      const S::Landing L = S::seek_one<R, decltype(c)::value>(V, i);
-      out->kv[i] = L.kv;
-      if (out->block) out->block[i] = L.block;
-      if (out->flags) out->flags[i] = L.flags;
-    }
-    return 0;
-  });
-  return PBL_OK;
+  return S::seek_host(host, n_blocks, q, nullptr, 0, out);
 }
 
 size_t pbl_seek_struct_layout(uint64_t* out, size_t cap) {

@@ -77,6 +77,16 @@ struct GlobalReader {
     be16(a, w0, w1);
     if (n < 16) keep(n, w0, w1);
   }
+  // 16 bytes as four little-endian words; the words past the first n bytes hold
+  // whatever follows the key (filter_core.hip.h uses only the bytes inside it)
+  static __device__ __forceinline__ void load_le16(gptr<const uint8_t> a, uint64_t, uint32_t w[4]) {
+    const gptr<const u64u> q = (gptr<const u64u>)a;
+    const uint64_t x = q[0], y = q[1];
+    w[0] = uint32_t(x);
+    w[1] = uint32_t(x >> 32);
+    w[2] = uint32_t(y);
+    w[3] = uint32_t(y >> 32);
+  }
 };
 
 // The arrays of a decoded batch and of the queries, through R's pointers.

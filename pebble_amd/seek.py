@@ -63,12 +63,15 @@ def prepare(decoded: DecodedBatch, comparer: int, stream=None) -> SeekIndex:
 
 def seek(decoded: DecodedBatch, keys: Keys, *, op: str = "ge", comparer: int,
          blocks=None, hide_obsolete_points: bool = False, index: Optional[SeekIndex] = None,
-         stream=None) -> SeekResult:
+         stream=None, filter: Optional[torch.Tensor] = None) -> SeekResult:
     """Seek every key.  `keys`: a list of bytes, or (uint8 tensor readable 16 B
     past the last key, int64 offsets [n + 1]) already on the device.  `blocks`
     (a sequence or an int32 device tensor, one block id per key) selects
     per-block mode; without it the seek is over the whole batch, with `index`
-    or an index built here."""
+    or an index built here.  `filter` (a table's bloom filter block, a uint8
+    device tensor; table mode and "ge" only) makes it SeekPrefixGE: a key whose
+    Split-prefix the filter excludes is answered -1 with PBL_SEEK_FILTERED and
+    not searched (pbl_seek_prefix_batch)."""
     dev = decoded.trailer.device
     if isinstance(keys, tuple):
         kb, ko = keys
@@ -95,16 +98,21 @@ def seek(decoded: DecodedBatch, keys: Keys, *, op: str = "ge", comparer: int,
     out = N.SeekOutC(kv.data_ptr(), ob.data_ptr(), fl.data_ptr())
     o = decoded.c_struct()
     ws = index.workspace if (index is not None and blk is None) else None
-    rc = N.lib().pbl_seek_batch(ctypes.byref(o), decoded.n_blocks, ctypes.byref(q), ctypes.byref(out),
-                                ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                ws.numel() if ws is not None else 0, _stream_handle(stream))
+    wp, wn = (ctypes.c_void_p(ws.data_ptr()), ws.numel()) if ws is not None else (None, 0)
+    if filter is not None:
+        rc = N.lib().pbl_seek_prefix_batch(ctypes.byref(o), decoded.n_blocks, ctypes.byref(q),
+                                           ctypes.c_void_p(filter.data_ptr()), int(filter.numel()),
+                                           ctypes.byref(out), wp, wn, _stream_handle(stream))
+    else:
+        rc = N.lib().pbl_seek_batch(ctypes.byref(o), decoded.n_blocks, ctypes.byref(q), ctypes.byref(out), wp, wn,
+                                    _stream_handle(stream))
     if rc != N.PBL_OK:
         raise DecodeError(f"pbl_seek_batch failed: {N.STATUS_NAMES.get(rc, rc)}")
     return SeekResult(kv[:n], ob[:n], fl[:n])
 
 
 def seek_host(host: dict, keys: Sequence[bytes], *, op: str = "ge", comparer: int, blocks=None,
-              hide_obsolete_points: bool = False):
+              hide_obsolete_points: bool = False, filter: Optional[bytes] = None):
     """The same seek over host arrays (`DecodedBatch.to_host()` or the
     oracle's dict) through pbl_seek_batch_host: (kv uint64 with PBL_SEEK_NONE,
     block uint32, flags uint8) as numpy."""
@@ -126,7 +134,12 @@ def seek_host(host: dict, keys: Sequence[bytes], *, op: str = "ge", comparer: in
     q = N.SeekQueriesC(kb.ctypes.data, ko.ctypes.data, blk.ctypes.data if blk is not None else None, n, comparer,
                        OPS[op], 1 if hide_obsolete_points else 0)
     out = N.SeekOutC(kv.ctypes.data, ob.ctypes.data, fl.ctypes.data)
-    rc = N.lib().pbl_seek_batch_host(ctypes.byref(o), nb, ctypes.byref(q), ctypes.byref(out))
+    if filter is not None:  # pbl_seek_prefix_batch_host: SeekPrefixGE behind the table's bloom filter
+        fb = np.frombuffer(bytes(filter) or b"\0", np.uint8)
+        rc = N.lib().pbl_seek_prefix_batch_host(ctypes.byref(o), nb, ctypes.byref(q), fb.ctypes.data, len(filter),
+                                                ctypes.byref(out))
+    else:
+        rc = N.lib().pbl_seek_batch_host(ctypes.byref(o), nb, ctypes.byref(q), ctypes.byref(out))
     if rc != N.PBL_OK:
         raise DecodeError(f"pbl_seek_batch_host failed: {N.STATUS_NAMES.get(rc, rc)}")
     return kv[:n], ob[:n], fl[:n]

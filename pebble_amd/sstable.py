@@ -246,6 +246,7 @@ class Table:
         self._props = None
         self._seek = None
         self._scan = {}
+        self._filter = False  # not read yet (None: the table has no bloom filter)
 
     # -- the physical step for any set of handles already on the device ----------
     def _blocks(self, off: torch.Tensor, length: torch.Tensor, fmt: int, flags: int = 0) -> BlockBatch:
@@ -489,11 +490,59 @@ class Table:
     def seek_lt(self, keys):
         return self._seek_op(keys, "lt")
 
-    def get(self, keys) -> torch.Tensor:
+    def get(self, keys, use_filter: bool = False) -> torch.Tensor:
         """Per key, the index of the first KV whose user key equals it
-        (PBL_SEEK_EXACT), else -1: int64 [n]."""
-        r = self.seek_ge(keys)
+        (PBL_SEEK_EXACT), else -1: int64 [n].  With `use_filter` the table's
+        bloom filter is asked first (`seek_prefix_ge`); a bloom filter has no
+        false negatives, so the result is the same."""
+        r = self.seek_prefix_ge(keys) if use_filter else self.seek_ge(keys)
         return torch.where((r.flags & N.PBL_SEEK_EXACT) != 0, r.kv, torch.full_like(r.kv, -1))
+
+    # -- the table filter (pebble_amd.filter; DESIGN.md §3.17) ----------------------
+    def filter(self) -> Optional[torch.Tensor]:
+        """The table's bloom filter block as a uint8 device tensor (the
+        metaindex's "fullfilter.rocksdb.BuiltinBloomFilter" entry,
+        layout.go:1119, through the physical step), or None when the table has
+        none.  A table that carries only a filter of another family is a table
+        without a filter.  A trailer that does not match the block's length
+        raises DecodeError."""
+        if self._filter is False:
+            from .filter import FILTER_NAME, probe
+            h = self.metaindex().get(FILTER_NAME)
+            if h is None:
+                self._filter = None
+                return None
+            bb = self._handle_blocks([h], N.PBL_FMT_ROW)
+            o, ln = int(bb.block_off[0].item()), int(bb.block_len[0].item())
+            f = bb.blocks[o:o + ln]
+            if int(probe([f], [b""], N.PBL_CMP_DEFAULT).status[0].item()) != N.PBL_OK:
+                raise DecodeError("bloom filter: unexpected cache line size")
+            self._filter = f
+        return self._filter
+
+    def may_contain(self, keys) -> torch.Tensor:
+        """TableFilterDecoder.MayContain of every key's Split-prefix: bool [n],
+        all true for a table without a filter."""
+        from .filter import probe
+        f = self.filter()
+        if f is None:
+            n = int(keys[1].numel()) - 1 if isinstance(keys, tuple) else len(keys)
+            return torch.ones(n, dtype=torch.bool, device=self.device)
+        r = probe([f], keys, self.comparer(), device=self.device)
+        return (r.may[0] & N.PBL_FILTER_MAY) != 0
+
+    def seek_prefix_ge(self, keys):
+        """singleLevelIterator.SeekPrefixGE with the filter block, the prefix
+        being each key's own Split-prefix: a SeekResult in which a key the filter
+        excludes has kv -1 and PBL_SEEK_FILTERED, and every other key what
+        `seek_ge` gives it (one launch, pbl_seek_prefix_batch).  Without a
+        filter this is `seek_ge`."""
+        f = self.filter()
+        if f is None:
+            return self.seek_ge(keys)
+        from .seek import seek
+        d, idx = self._seekable()
+        return seek(d, keys, op="ge", comparer=idx.comparer, index=idx, filter=f)
 
     # -- range scans over the decoded table (pebble_amd.scan) ----------------------
     def _scannable(self, resolve: bool, hide: bool, n: int):
