@@ -1591,6 +1591,148 @@ int pbl_seek_prefix_batch(const pbl_decode_out* decoded, uint32_t n_blocks, cons
 int pbl_seek_prefix_batch_host(const pbl_decode_out* host, uint32_t n_blocks, const pbl_seek_queries* q,
                                const uint8_t* filter, uint64_t filter_len, pbl_seek_out* out);
 
+/* ---- compaction view of a sorted decoded batch, on the device ----
+ * What compact.Iter (internal/compact/iterator.go) returns over the point keys
+ * of a block: not what a reader sees (pbl_visible_batch) but what a compaction
+ * must KEEP.  Input as pbl_visible_batch takes it: one decoded batch whose
+ * blocks are each sorted under (comparer, trailer descending); one comes out
+ * with the same n_blocks, result block q being First(); Next()... of the
+ * reference over block q with DefaultMerger.  Blocks are independent, there is
+ * no visibility cut: every KV takes part.
+ *
+ *   snapshots   ascending sequence numbers, any number including none
+ *   PBL_COMPACT_ELIDE_TOMBSTONES  ElideTombstonesOutsideOf(nil): every point
+ *                                 tombstone may be elided
+ *   PBL_COMPACT_BOTTOMMOST        IterConfig.IsBottommostDataLayer
+ *
+ * Stripes and segments.  A KV's stripe is Snapshots.Index(seq), the number of
+ * snapshots <= seq (snapshots.go:50-54).  A segment is a maximal run of KVs of
+ * a block with equal user key (key_cmp == 0) and equal stripe.  The iterator's
+ * state never crosses a segment boundary (nextInStripe, iterator.go:778-851).
+ * Inside a segment the reference processes a HEAD, which decides what happens
+ * to the KVs after it; below, "elided" means ELIDE_TOMBSTONES and stripe 0,
+ * "tombstone" one of DEL / SINGLEDEL / DELSIZED, and "the rest is skipped"
+ * that no later KV of the segment is a head (skipInStripe, :726-737).  A DEL's
+ * and a SINGLEDEL's value bytes are never read: they are value-less (:605,
+ * :1010).
+ *
+ * Head rules (Iter.Next, :439-704):
+ *  DEL / DELSIZED, elided (:576-593): nothing is emitted, the rest is skipped.
+ *  SINGLEDEL, elided (skipDueToSingleDeleteElision, :1099-1185): nothing is
+ *     emitted.  The next KV of the segment: a SINGLEDEL repeats the rule (one
+ *     ineffectual call); DEL / DELSIZED (one ineffectual call) and SETWITHDEL
+ *     skip the rest; a SET / MERGE is consumed and the KV after it is a fresh
+ *     head.  The segment ending on the pending SINGLEDEL: one ineffectual call.
+ *  DEL otherwise (:603-607): emitted with an empty value; the rest is skipped.
+ *  SET (setNext, :853-905): emitted with its own value; the kind becomes
+ *     SETWITHDEL iff a tombstone follows anywhere in the segment; the rest is
+ *     skipped.  SETWITHDEL: emitted as it is; the rest is skipped.
+ *  MERGE (mergeNext, :907-992): the following MERGEs of the segment are
+ *     operands; a SET / SETWITHDEL is the last operand and makes the kind SET; a
+ *     tombstone ends the chain without being an operand and makes the kind
+ *     SETWITHDEL; a chain that reaches the segment's end stays MERGE.  The
+ *     value is the operands' values concatenated OLDEST FIRST, as
+ *     pbl_visible_batch.  The rest is skipped.
+ *  SINGLEDEL otherwise (singleDeleteNext, :1004-1087): the next KV of the
+ *     segment decides.  None: emitted as SINGLEDEL.  DEL / DELSIZED (one
+ *     ineffectual call) or SETWITHDEL: emitted with kind DEL and its own
+ *     sequence number, the rest is skipped.  SINGLEDEL: one ineffectual call, it
+ *     is passed over and the FIRST one's key and trailer are kept.  SET / MERGE:
+ *     consumed together with it, nothing is emitted, and the KV after it is a
+ *     fresh head.
+ *     After a consumed SET / MERGE (elided or not), a next KV of the same user
+ *     key (in any stripe) of kind SET / SETWITHDEL / MERGE is one
+ *     nondeterministic call (:1049-1073, :1151-1176).
+ *  DELSIZED otherwise (deleteSizedNext, :1193-1363): emitted; it holds a value,
+ *     at first its own.  Every following KV of the segment:
+ *       a tombstone: if the held value is not empty, one missized DELSIZED; the
+ *         held value becomes that KV's (empty for DEL / SINGLEDEL); a DEL or
+ *         SINGLEDEL makes the kind DEL and the rest is skipped;
+ *       SET / MERGE / SETWITHDEL with an empty held value: kind DEL, the rest is
+ *         skipped;
+ *       the same with a held value: it is one uvarint, the expected size; if
+ *         len(that KV's user key) + len(its value) differs, one missized
+ *         DELSIZED, kind DEL, empty value, the rest is skipped; if it matches,
+ *         the held value becomes empty and the walk goes on.
+ *     The result's value is the held value at the segment's end.  A held value
+ *     that is not exactly one uvarint where the reference decodes it (:1249,
+ *     :1308: at any following KV) is corruption: PBL_CORRUPT_BOUNDS.
+ *  With PBL_COMPACT_BOTTOMMOST in stripe 0 (:659-666, :862-864): an emitted SET /
+ *     SETWITHDEL / MERGE head gets sequence number 0, and a MERGE that stayed
+ *     MERGE becomes SET.
+ *
+ * A result KV carries the head's key bytes, the rewritten trailer, the value
+ * as above, and the head's entry_off, tiering meta and value-kind flag bits, as
+ * the visible view does.  Optional outputs per result KV: src_kv (the head's
+ * index in the input), n_src (the operands of a MERGE chain, 1 otherwise) and
+ * pinned (Iter.SnapshotPinned(), :392, :482, :598): 1 when the head starts its
+ * segment and the KV before it has the same user key, or when the head is a
+ * tombstone, ELIDE_TOMBSTONES is set and its stripe is not 0.  Optional outputs
+ * per block, zero for a block that is not PBL_OK: n_missized
+ * (IterStats.CountMissizedDels), n_ineffectual and n_nondeterministic (the
+ * calls of IneffectualSingleDeleteCallback / NondeterministicSingleDeleteCallback).
+ *
+ * Statuses: a result block is empty, its neighbours unaffected, when (first
+ * that applies)
+ *   - the input block is not PBL_OK: that status;
+ *   - the block is not sorted; two KVs of one user key with equal sequence
+ *     numbers count as not sorted (:817-822): PBL_INVALID_ARG;
+ *   - a KV has PBL_KV_INVALID_KEY or a kind outside the six; a value that is a
+ *     handle takes part in a MERGE chain of more than one operand:
+ *     PBL_UNSUPPORTED;
+ *   - a DELSIZED value as above: PBL_CORRUPT_BOUNDS;
+ *   - the result's KVs reach 2^32 or its key or value bytes pass 4 GiB:
+ *     PBL_UNSUPPORTED.
+ * PBL_KV_OBSOLETE is ignored.
+ *
+ * Sizing, overflow, workspace and n_kv as pbl_visible_*; with PBL_COMPACT_SIZED
+ * pbl_compact_batch takes everything from the workspace as the last
+ * pbl_compact_size over the same input, snapshots and flags left it.
+ * PBL_INVALID_ARG before any device call as there, and for unknown flags
+ * (PBL_COMPACT_SIZED is unknown to pbl_compact_size and the host form) and
+ * n_snapshots != 0 with a NULL list.  The snapshot list is DEVICE memory for
+ * the device calls, which cannot see its order; the host form checks that it
+ * ascends (non-strictly) and answers PBL_INVALID_ARG otherwise.
+ *
+ * Out of scope: range deletions and range keys in the stream,
+ * elision by key ranges, user and deletable mergers, blob values in chains,
+ * output splitting.
+ */
+#define PBL_COMPACT_SIZED 0x1u             /* pbl_compact_batch: the workspace holds the last pbl_compact_size */
+#define PBL_COMPACT_ELIDE_TOMBSTONES 0x2u
+#define PBL_COMPACT_BOTTOMMOST 0x4u
+
+typedef struct pbl_compact_in {
+  pbl_decode_out batch;  /* the arrays are DEVICE (HOST for pbl_compact_batch_host); capacities and workspace fields unused */
+  uint32_t n_blocks, comparer /* PBL_CMP_* */;
+  uint64_t n_kv;              /* as pbl_visible_in; unused by pbl_compact_batch_host */
+  const uint64_t* snapshots;  /* [n_snapshots] ascending; DEVICE (HOST for the host form) */
+  uint64_t n_snapshots;
+} pbl_compact_in;
+
+typedef struct pbl_compact_out {
+  pbl_decode_out result;  /* one block per q; workspace fields unused */
+  uint64_t* src_kv;       /* [result.kv_cap], optional */
+  uint32_t* n_src;        /* [result.kv_cap], optional */
+  uint8_t* pinned;        /* [result.kv_cap], optional */
+  uint32_t* n_missized;          /* [n_blocks], optional */
+  uint32_t* n_ineffectual;       /* [n_blocks], optional */
+  uint32_t* n_nondeterministic;  /* [n_blocks], optional */
+} pbl_compact_out;
+
+uint64_t pbl_compact_workspace_bytes(uint32_t n_blocks, uint64_t n_kv);
+int pbl_compact_size(const pbl_compact_in* in, pbl_compact_out* out, void* workspace, uint64_t workspace_bytes,
+                     uint32_t flags, void* stream);
+int pbl_compact_batch(const pbl_compact_in* in, pbl_compact_out* out, void* workspace, uint64_t workspace_bytes,
+                      uint32_t flags, void* stream);
+/* The same rules over HOST arrays as the sequential loop of the reference's
+ * shape (a different algorithm from the device's scans, so that the two check
+ * each other).  No device call, no workspace.  Single-threaded. */
+int pbl_compact_batch_host(const pbl_compact_in* in, pbl_compact_out* out, uint32_t flags);
+/* sizeof(pbl_compact_in), its 6 field offsets, sizeof(pbl_compact_out), its 7
+ * (the other layout lists are unchanged; ABI version 9 stands). */
+size_t pbl_compact_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ C-ABI declared in include/pebble_amd.h.  This package is the host layer:
   pebble_amd.scan    batched bounded scans over a DecodedBatch, on the device
   pebble_amd.merge   batched k-way merge of sorted DecodedBatches, on the device
   pebble_amd.visible the snapshot-visible view of a sorted DecodedBatch, and read()
+  pebble_amd.compact the compaction view of a sorted DecodedBatch (what compact.Iter keeps), and compact_tables()
   pebble_amd.rangedel range deletions in that path: the flattened set and the per-KV cover
   pebble_amd.rangekey range keys in that path: the coalesced set at a snapshot (host), the per-KV mask (device)
   pebble_amd.keyspan columnar keyspan blocks into runs, on the device; Writer for tests and tools

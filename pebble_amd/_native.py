@@ -241,6 +241,22 @@ class VisibleOutC(ctypes.Structure):  # pbl_visible_out
     _fields_ = [("result", DecodeOutC), ("src_kv", _vp), ("n_src", _vp)]
 
 
+# compaction view (pbl_compact_batch)
+PBL_COMPACT_SIZED = 0x1              # pbl_compact_batch flags
+PBL_COMPACT_ELIDE_TOMBSTONES = 0x2   # pbl_compact_size / pbl_compact_batch / pbl_compact_batch_host flags
+PBL_COMPACT_BOTTOMMOST = 0x4
+
+
+class CompactInC(ctypes.Structure):  # pbl_compact_in
+    _fields_ = [("batch", DecodeOutC), ("n_blocks", ctypes.c_uint32), ("comparer", ctypes.c_uint32),
+                ("n_kv", ctypes.c_uint64), ("snapshots", _vp), ("n_snapshots", ctypes.c_uint64)]
+
+
+class CompactOutC(ctypes.Structure):  # pbl_compact_out
+    _fields_ = [("result", DecodeOutC), ("src_kv", _vp), ("n_src", _vp), ("pinned", _vp), ("n_missized", _vp),
+                ("n_ineffectual", _vp), ("n_nondeterministic", _vp)]
+
+
 # range deletions in the read path (pbl_rangedel_set, pbl_rangedel_cover, the view's _rd entry points)
 PBL_RANGEDEL_MAX_RUNS = 16
 PBL_KIND_RANGEDEL = 15
@@ -407,6 +423,14 @@ SIGNATURES = {
     "pbl_seek_prefix_batch_host": (ctypes.c_int, [ctypes.POINTER(DecodeOutC), ctypes.c_uint32,
                                                   ctypes.POINTER(SeekQueriesC), _vp, ctypes.c_uint64,
                                                   ctypes.POINTER(SeekOutC)]),
+    "pbl_compact_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint64]),
+    "pbl_compact_size": (ctypes.c_int, [ctypes.POINTER(CompactInC), ctypes.POINTER(CompactOutC), _vp, ctypes.c_uint64,
+                                        ctypes.c_uint32, _vp]),
+    "pbl_compact_batch": (ctypes.c_int, [ctypes.POINTER(CompactInC), ctypes.POINTER(CompactOutC), _vp, ctypes.c_uint64,
+                                         ctypes.c_uint32, _vp]),
+    "pbl_compact_batch_host": (ctypes.c_int, [ctypes.POINTER(CompactInC), ctypes.POINTER(CompactOutC),
+                                              ctypes.c_uint32]),
+    "pbl_compact_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
