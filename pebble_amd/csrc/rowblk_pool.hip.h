@@ -14,12 +14,15 @@
 //   stage     the block HBM -> LDS by LDS-DMA, one round trip
 //   walk      lane per restart run (rowblk_writer.go:147-155 cuts the prefix
 //             chain there): headers parked in registers, a DPP scan places the
-//             runs, the block's aggregate is published
+//             runs, the block's aggregate is published.  One run per lane
+//             (up to 64 runs): 16 straight-line entries, no exec-masked
+//             branch on the common path, the failure causes looked at once
+//             after the loop (PBL_POOL_FRONT, round 12)
 //   meta      per-entry metadata words (key source, shared and key length,
 //             prefix parent, header length, flags) and per-KV value offsets
-//             written from the registers into the slot; the stage is released
-//             (before this pass when it reads the registers only:
-//             PBL_POOL_EARLYREL)
+//             written from the registers into the slot, 16 flat bodies; the
+//             stage is released (before this pass when it reads the registers
+//             only: PBL_POOL_EARLYREL)
 //   resolve   the exclusive prefix by decoupled look-back, issued together
 //             with the first step's and the restart words' loads
 //   prefetch  (PBL_POOL_PREFETCH, off by default: measured slower, DESIGN.md
@@ -592,6 +595,224 @@ __device__ __forceinline__ void meta_runs(Slot<kHide>& W, const View& V, uint32_
     M.prev_sh = M.pp = M.ppsh = 0;
     span_meta<kHide>(W, V, rw & kRestartMask, e0, rw, 0, 0, 0, flags, vprefix, M);
   }
+}
+
+// ---- the pool kernel's own front (PBL_POOL_FRONT) ----
+// The same walk and metadata pass for the one-run-per-lane case, written so
+// that the lanes execute fewer instructions and waits: every value, every
+// fallback and the slot layout are the forms' above (which the row-wave and
+// mixed kernels keep).
+//   walk   one entry's body is straight-line: a lane past its run's end, or
+//          one that has failed, goes on with pos clamped to the restart table
+//          (inside the stage) and its results unused; the failure causes are
+//          OR-ed into flags looked at once after the loop.  Whether entries
+//          need their kind byte at all (kCls) is decided per block, and the
+//          header's three-one-byte-varints form by a ballot of the live lanes.
+//   meta   the parked entries are 16 flat bodies, the state carried by plain
+//          arithmetic (a lane's parked entries are its first B.n, so nothing
+//          after them reads it), the stores alone under `k < B.n`; the value-
+//          prefix byte only in the kVp form; m0 built as two 32-bit halves.
+// 0: the shared forms, as before round 12.
+#ifndef PBL_POOL_FRONT
+#define PBL_POOL_FRONT 1
+#endif
+constexpr bool kFront = PBL_POOL_FRONT != 0;
+
+// hdr3 out of line (the walk's 16 unrolled entries would each carry a copy of
+// a form that few blocks reach): shared, unshared, value length, header length
+// | ok << 3.  One- and two-byte varints included: what hdr2 returns.
+__device__ __noinline__ uint4 hdr3_out(uint64_t w) {
+  uint32_t sh, un, vl, h;
+  const bool ok = hdr3(w, &sh, &un, &vl, &h);
+  return make_uint4(sh, un, vl, (h & 7u) | uint32_t(ok) << 3);
+}
+
+// hdr2 for a whole wave: the one-byte form when every live lane has it (no
+// divergent region), the branch-free 1..3-byte form for all lanes otherwise.
+__device__ __forceinline__ bool hdr2_wave(uint64_t w, bool live, uint32_t* sh, uint32_t* un, uint32_t* vl,
+                                          uint32_t* h) {
+  if (__builtin_amdgcn_ballot_w64(live && (uint32_t(w) & 0x808080u) != 0) == 0) {
+    *sh = uint32_t(w) & 0xffu;
+    *un = uint32_t(w >> 8) & 0xffu;
+    *vl = uint32_t(w >> 16) & 0xffu;
+    *h = 3;
+    return true;
+  }
+  const uint4 r = hdr3_out(w);
+  *sh = r.x;
+  *un = r.y;
+  *vl = r.z;
+  *h = r.w & 7u;
+  return (r.w >> 3) != 0;
+}
+
+// run_walk for every lane of the wave at once (r >= nres: a lane without a
+// run).  kCls: entries are classified by their kind byte (entry_class's rules).
+template <bool kHide, bool kCls>
+__device__ __forceinline__ void run_walk_flat(const View& V, uint32_t r, uint32_t nres, uint32_t roff, uint32_t flags,
+                                              bool vprefix, PRun& B, PAcc& acc, bool& ok, bool& bad, bool& vbad,
+                                              bool& over) {
+  // run_bounds: both restart words in one read (the last run's second word is
+  // the block's restart count: inside the block)
+  const uint32_t rc = min(r, nres - 1);
+  const uint64_t two = V.ld8(roff + 4 * rc);
+  B.rw = uint32_t(two);
+  const uint32_t s0 = B.rw & kRestartMask;
+  const uint32_t e0 = rc + 1 < nres ? (uint32_t(two >> 32) & kRestartMask) : roff;
+  const bool bok = (rc != 0 || s0 == 0) && s0 < e0 && e0 <= roff;
+  const uint32_t tsub = (flags & PBL_ROW_RAW_KEYS) ? 0u : 8u;  // trailer bytes of a key
+  bool live = r < nres && bok, fail = r < nres && !bok;
+  // pos stays inside [0, roff] whatever the lane has read (a lane that is not
+  // live reads some 8 bytes of the block), so the next entry's read waits for
+  // this entry's lengths only, not for its checks
+  uint32_t pos = min(s0, roff), n = 0, cnt = 0, kb = 0, vb = 0, prev_kl = 0, prev_kind = 0;
+#pragma unroll
+  for (int k = 0; k < kRunBuf; k++) {
+    const uint32_t p = pos;
+    uint32_t sh, un, vl, h;
+    const bool hok = hdr2_wave(V.ld8(p), live, &sh, &un, &vl, &h);
+    const uint32_t np = p + h + un + vl;  // < 2^23: no overflow
+    const uint32_t kl = sh + un;
+    const bool g1 = hok && (k != 0 || sh == 0) && np <= e0;
+    if (k > 0) bad = bad || (live && g1 && sh > prev_kl);
+    bool g2 = g1 && kl <= kMaxKl, hidden = false, setv = false;
+    uint32_t vlen = vl;
+    if constexpr (kCls) {
+      // the kind byte: key byte kl - 8, among the unshared bytes (un >= 8) or
+      // the previous key's when that has the same length
+      const bool has = kl >= 8, own = kl >= sh + 8;
+      const uint32_t kbyte = V.byte(live && g2 && own ? p + h + (un - 8) : 0u);  // < np <= e0
+      const uint32_t kind = own ? kbyte : prev_kind;
+      g2 = g2 && (!has || own || (k > 0 && prev_kl == kl));
+      hidden = kHide && has && (kind & 64u);
+      setv = vprefix && has && !hidden && (kind & 0xBFu) == 1;
+      prev_kind = has ? kind : prev_kind;
+      if (vprefix) {  // uniform
+        const bool rd = live && g2 && setv;
+        vbad = vbad || (rd && vl == 0);
+        const uint32_t pre = V.byte(rd && vl != 0 ? p + h + un : 0u);  // < np <= e0
+        if (rd && vl != 0 && ((pre & 0xC0) == 0 || (flags & PBL_ROW_NO_VALUER))) vlen--;
+      }
+    }
+    const bool take = live && g2, vis = take && !hidden;
+    fail = fail || (live && !g2);
+    B.ea[k] = p | uint32_t(hidden) << 15 | sh << 16 | uint32_t(setv) << 31;
+    B.eb[k] = un | (h << 14) | (vl << 17);
+    n += take;
+    cnt += vis;
+    kb += vis ? kl - min(kl, tsub) : 0u;
+    vb += vis ? vlen : 0u;
+    prev_kl = kl;
+    pos = min(np, roff);  // (live: np < e0 <= roff)
+    live = take && np < e0;
+  }
+  if (live) over = true;
+  if (fail) ok = false;
+  acc.ne += n;
+  acc.cnt += cnt;
+  acc.kb += kb;
+  acc.vb += vb;
+  B.n = n;
+  B.pos = pos;
+  B.e0 = e0;
+  B.prev_kl = prev_kl;
+  B.prev_kind = prev_kind;
+}
+
+// park_meta as flat bodies.  kVp: SET values carry a value prefix (the one
+// form that reads the stage).
+template <bool kHide, bool kVp>
+__device__ __forceinline__ void park_meta_flat(Slot<kHide>& W, const View& V, const PRun& B, uint32_t flags,
+                                               MState& M) {
+  const uint32_t tmin = (flags & PBL_ROW_RAW_KEYS) ? 0u : 8u;
+  const uint32_t fl0 = PBL_KV_RESTART | ((B.rw >> 31) ? PBL_KV_RESTART_SAMEPFX : 0u);
+#pragma unroll
+  for (int k = 0; k < kRunBuf; k++) {
+    const uint32_t ea = B.ea[k], eb = B.eb[k];
+    const uint32_t pos = ea & 0x7fffu, sh = (ea >> 16) & 0x7fffu, un = eb & 0x3fffu, h = (eb >> 14) & 7u, vl = eb >> 17;
+    const bool on = uint32_t(k) < B.n, hidden = kHide && ((ea >> 15) & 1u);
+    const uint32_t kl = sh + un;
+    uint32_t par = M.e, parsh = 0;
+    if (k > 0) {  // (a run's first entry shares nothing)
+      const bool up = M.prev_sh >= sh;
+      uint32_t c = up ? M.pp : M.e - 1, csh = up ? M.ppsh : M.prev_sh;
+      if (on && sh != 0) {
+        while (csh >= sh) {
+          c = m_par(W.m0[c]);
+          csh = m_sh(W.m0[c]);
+        }
+      }
+      par = sh != 0 ? c : M.e;
+      parsh = sh != 0 ? csh : 0u;
+    }
+    uint32_t vs = pos + h + un, vlen = vl, fl = k == 0 ? fl0 : 0u;
+    if (kl < tmin) fl |= PBL_KV_INVALID_KEY;
+    if constexpr (kVp) {
+      const bool setv = on && (ea >> 31);
+      const uint32_t pre = V.byte(setv ? vs : 0u);
+      const bool strip = (pre & 0xC0) == 0 || (flags & PBL_ROW_NO_VALUER);
+      if (setv) {
+        vs += strip;
+        vlen -= strip;
+        fl |= strip ? 0u : (pre & 0xC0) == 0x80 ? PBL_KV_VALBLK_HANDLE : PBL_KV_BLOB_HANDLE;
+      }
+    }
+    // m_pack in halves: bit 32 falls inside the key length
+    const uint32_t lo = (pos + h) | sh << 15 | kl << 27, hi = kl >> 5 | par << 7 | h << 16 | fl << 20;
+    if (on) {
+      W.m0[M.e] = uint64_t(hi) << 32 | lo;
+      if (!hidden) {
+        if (kHide) W.ent[M.v] = uint16_t(M.e);
+        W.vp[M.v] = M.vb | (vs << 16);
+      }
+    }
+    const bool vis = on && !hidden;
+    M.vb += vis ? vlen : 0u;
+    M.v += vis;
+    M.prev_sh = sh;
+    M.pp = par;
+    M.ppsh = parsh;
+    M.e += on;
+  }
+}
+
+// walk_runs / meta_runs of the pool kernel: the flat forms where a lane has
+// one run at most, the shared forms otherwise.
+template <bool kHide>
+__device__ __forceinline__ void front_walk(const View& V, uint32_t r0, uint32_t r1, uint32_t nres, uint32_t roff,
+                                           uint32_t flags, bool vprefix, bool single, PRun& RB, PAcc& acc, bool& ok,
+                                           bool& bad, bool& vbad, bool& over) {
+  if (!kFront) {
+    walk_runs<kHide>(V, r0, r1, nres, roff, flags, vprefix, single, RB, acc, ok, bad, vbad, over);
+    return;
+  }
+  if (!single) {  // (the constant: the shared single-run form is not instantiated here)
+    walk_runs<kHide>(V, r0, r1, nres, roff, flags, vprefix, false, RB, acc, ok, bad, vbad, over);
+    return;
+  }
+  if ((kHide || vprefix) && !(flags & PBL_ROW_RAW_KEYS))
+    run_walk_flat<kHide, true>(V, r0, nres, roff, flags, vprefix, RB, acc, ok, bad, vbad, over);
+  else
+    run_walk_flat<kHide, false>(V, r0, nres, roff, flags, vprefix, RB, acc, ok, bad, vbad, over);
+  if (over && ok)
+    count_span<kHide>(V, RB.pos, RB.e0, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, acc, ok, bad, vbad);
+}
+
+template <bool kHide>
+__device__ __forceinline__ void front_meta(Slot<kHide>& W, const View& V, uint32_t r0, uint32_t r1, uint32_t nres,
+                                           uint32_t roff, uint32_t flags, bool vprefix, bool single, bool over,
+                                           const PRun& RB, MState& M) {
+  if (!kFront) {
+    meta_runs<kHide>(W, V, r0, r1, nres, roff, flags, vprefix, single, over, RB, M);
+    return;
+  }
+  if (!single) {
+    meta_runs<kHide>(W, V, r0, r1, nres, roff, flags, vprefix, false, over, RB, M);
+    return;
+  }
+  if (vprefix) park_meta_flat<kHide, true>(W, V, RB, flags, M);
+  else park_meta_flat<kHide, false>(W, V, RB, flags, M);
+  if (over) span_meta<kHide>(W, V, RB.pos, RB.e0, RB.rw, RB.n, RB.prev_kl, RB.prev_kind, flags, vprefix, M);
 }
 
 // The block's bytes in global memory for the emits (the stage is gone by
@@ -1396,7 +1617,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
     RB.n = 0;
     RB.pos = RB.e0 = RB.prev_kl = RB.prev_kind = RB.rw = 0;
     const bool single = R == 1;
-    walk_runs<kHide>(V, r0, r1, nres, roff, flags, vprefix, single, RB, acc, ok, bad, vbad, over);
+    front_walk<kHide>(V, r0, r1, nres, roff, flags, vprefix, single, RB, acc, ok, bad, vbad, over);
     const uint32_t ic = dpp_incl_scan(acc.cnt), ik = dpp_incl_scan(acc.kb), iv = dpp_incl_scan(acc.vb);
     const uint32_t ie = kHide ? dpp_incl_scan(acc.ne) : ic;
     nkv = last_lane(ic);
@@ -1422,7 +1643,7 @@ __device__ __forceinline__ Pend block_front(PoolLds<kHide>& L, uint32_t s, uint3
         PSTAMP(A, b, 9, l == 0);
       }
       MState M{ie - (kHide ? acc.ne : acc.cnt), ic - acc.cnt, iv - acc.vb, 0, 0, 0};
-      meta_runs<kHide>(W, V, r0, r1, nres, roff, flags, vprefix, single, over, RB, M);
+      front_meta<kHide>(W, V, r0, r1, nres, roff, flags, vprefix, single, over, RB, M);
       if (l < 5) W.vp[nkv + l] = tvb;
       PSTAMP(A, b, 4, l == 0);
     }
