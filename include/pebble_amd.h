@@ -1733,6 +1733,160 @@ int pbl_compact_batch_host(const pbl_compact_in* in, pbl_compact_out* out, uint3
  * (the other layout lists are unchanged; ABI version 9 stands). */
 size_t pbl_compact_struct_layout(uint64_t* out, size_t cap);
 
+/* ---- row-block encoder: a sorted decoded batch back into data blocks ----
+ * The write side of the row format as a batch operation: a decoded batch goes
+ * in, finished row-format data blocks come out, cut where Pebble's table writer
+ * cuts them and byte for byte what RawRowWriter + rowblk.Writer produce
+ * (sstable/rowblk/rowblk_writer.go:128-320; RawRowWriter.addPoint /
+ * makeAddPointDecisionV3 / shouldFlush, sstable/rowblk_writer.go:585-774,
+ * :1238-1262; FlushGovernor without size classes,
+ * sstable/block/flush_governor.go:103-143).
+ *
+ * Block q of the input is one STREAM: an independent sorted sequence of KVs
+ * (one range of a compact_tables result, say).  Every stream is encoded as if
+ * by a fresh table writer and its output blocks are consecutive.  A stream
+ * without KVs, or whose blk_status is not PBL_OK, produces no blocks;
+ * stream_status[q] carries the input status.  Input values carry no value
+ * prefix byte (what a decode with PBL_ROW_VALUE_PREFIX | PBL_ROW_NO_VALUER
+ * yields).  "Predecessor" below is the previous KV of the stream, whichever
+ * block it went to.
+ *
+ * Options: restart_interval ri >= 1; target_block_size in [1, 2^31);
+ * block_size_threshold (percent); comparer (PBL_CMP_*: Split and Compare);
+ * flags PBL_ENC_VALUE_PREFIX (TableFormat >= Pebblev3), PBL_ENC_OBSOLETE
+ * (>= Pebblev4; without VALUE_PREFIX: PBL_INVALID_ARG), PBL_ENC_LOWEST_LEVEL
+ * (writingToLowestLevel).  low = (target * threshold + 99) / 100, high = target.
+ *
+ *  1 Internal key = user key || LE64(trailer); a KV written obsolete has the
+ *    trailer OR-ed with the obsolete bit (64) first.
+ *  2 Shared prefix.  Entries 0, ri, 2 ri, ... OF THEIR BLOCK are restarts and
+ *    share 0 bytes.  Any other entry shares the common prefix of its internal
+ *    key and its predecessor's, capped at min(max_shared, both lengths).
+ *    Without VALUE_PREFIX max_shared = len(user key), so that a predecessor
+ *    whose user key is shorter lets the comparison run into its trailer bytes
+ *    ("k"#..,SET before "k\x01.." shares 2 bytes): internal-key bytes are
+ *    compared, not user keys.  With VALUE_PREFIX max_shared = Split(the
+ *    predecessor's user key).
+ *  3 set_same(k), with VALUE_PREFIX: k has a predecessor, both kinds are SET and
+ *    Compare(prev[:Split(prev)], cur[:Split(cur)]) == 0.  A SET's stored value
+ *    is the byte InPlaceValuePrefix(set_same) (0x00 / 0x20, sstable/block/
+ *    kv.go:75-81) and then the value; every other kind stores the value bare.
+ *    Without the flag set_same is false and nothing is prefixed.  Value blocks
+ *    are not built: every value is stored in place.
+ *  4 Obsolete, with OBSOLETE:
+ *      obs(k) = force(k) || (pred(k) && C3(k)) ||
+ *               (same_user_key(k) && (obs(k-1) || kind(k-1) != MERGE))
+ *    force = the input's PBL_KV_OBSOLETE flag (forceObsolete); C3 =
+ *    LOWEST_LEVEL and kind in {DEL, SINGLEDEL, DELSIZED}; pred(k): k has a
+ *    predecessor (makeAddPointDecisionV3 returns before C3 for a table's first
+ *    point key, :590-592); same_user_key: Compare == 0 with the predecessor.
+ *    Without the flag nothing is written obsolete and input flags are ignored.
+ *  5 Entry = uvarint(shared) uvarint(len(ikey) - shared) uvarint(len(stored
+ *    value)) ikey[shared:] stored value.
+ *  6 Restart word r of a block = the offset of block entry r * ri; bit 31 is set
+ *    iff r >= 1 and set_same held for each of the entries (r-1) ri + 1 .. r ri.
+ *    Restart 0 never has it (the table writer resets the block writer).  Block
+ *    tail: the restart words, then their count, LE32 each.
+ *  7 Flush.  With S(i, j) = EstimatedSize of the block of stream KVs i .. j-1
+ *    (entry bytes + 4 per restart + 4), the block that starts at KV i ends
+ *    before the first j > i for which
+ *      S(i, j) >= low  and
+ *      S(i, j) + len(ikey_j) + len(stored value_j) + (4 if (j - i) % ri == 0)
+ *        + 4 + uvarint_len(len(ikey_j)) + uvarint_len(len(stored value_j)) > high
+ *    (the reference's overestimate: 4 bytes for the shared varint, the whole
+ *    key).  A block below low takes the next KV however large.
+ *  8 Key order is not checked (disableKeyOrderChecks): the input is sorted by
+ *    contract.  With target < 2^31 no block's entry area reaches 2^31 bytes
+ *    before its last entry, so ErrBlockTooBig cannot arise; a stream holding a
+ *    KV whose entry alone is 2^31 bytes or more is PBL_UNSUPPORTED (its block
+ *    length would not fit 32 bits) and produces no blocks.
+ *
+ * Outputs (caller-allocated; DEVICE, HOST for the host form):
+ *   blocks            block b at blocks[block_off[b] .. + block_len[b]); block_off
+ *                     is 16-byte aligned, blocks follow each other, and the bytes
+ *                     from a block's end to the next 16-byte boundary are zero: the
+ *                     three arrays are a pbl_block_batch for pbl_decode_batch
+ *   block_stream, block_first_kv (index into the batch's KV arrays), block_n_kv
+ *                     what an index entry is made of: the block's last key is KV
+ *                     first + n - 1, the next block's first key KV first + n
+ *   stream_block_base [n_streams + 1]: stream q's blocks are [base[q], base[q+1])
+ *   stream_status     [n_streams]
+ *   obsolete          [n_kv], optional: the bit each KV was written with (0 for
+ *                     KVs of streams that produced nothing)
+ *   totals            blocks, bytes of `blocks` needed (a multiple of 16),
+ *                     restart words, OR of (1u << status) over streams that are
+ *                     not OK, and their number
+ * pbl_rowenc_size writes totals, stream_block_base and stream_status only (the
+ * other pointers and the capacities are ignored) and leaves the partition in
+ * the workspace; pbl_rowenc_batch with PBL_ROWENC_SIZED takes it from there
+ * (same input, options and workspace), without it computes it first.  When
+ * n_blocks > block_cap or block_bytes > blocks_cap every size is still written
+ * (totals, stream_block_base, stream_status), totals.status_mask has
+ * 1u << PBL_OVERFLOW, and the block arrays and bytes are unspecified.  in->n_kv
+ * is the batch's totals.n_kv as the host read it (below 2^32 - 1).  The
+ * workspace is DEVICE memory, 16-byte aligned, of pbl_rowenc_workspace_bytes.
+ * PBL_INVALID_ARG before any device call: NULL arguments, an input batch that
+ * lacks an array the rules read, options out of range, unknown flags, a short
+ * or misaligned workspace.
+ */
+#define PBL_ENC_VALUE_PREFIX 0x1u
+#define PBL_ENC_OBSOLETE 0x2u
+#define PBL_ENC_LOWEST_LEVEL 0x4u
+#define PBL_ROWENC_SIZED 0x1u /* pbl_rowenc_batch flags: the workspace holds the last pbl_rowenc_size */
+
+typedef struct pbl_rowenc_opts {
+  uint32_t restart_interval;
+  uint32_t target_block_size;
+  uint32_t block_size_threshold; /* percent */
+  uint32_t comparer;             /* PBL_CMP_* */
+  uint32_t flags;                /* PBL_ENC_* */
+  uint32_t reserved;
+} pbl_rowenc_opts;
+
+typedef struct pbl_rowenc_in {
+  pbl_decode_out batch; /* the arrays are DEVICE (HOST for the host form); capacities and workspace fields unused */
+  uint32_t n_streams;   /* the batch's blocks */
+  uint32_t reserved;
+  uint64_t n_kv;        /* unused by pbl_rowenc_batch_host */
+} pbl_rowenc_in;
+
+typedef struct pbl_rowenc_totals {
+  uint64_t n_blocks;
+  uint64_t block_bytes;
+  uint64_t n_restarts;
+  uint32_t status_mask;
+  uint32_t n_bad_streams;
+} pbl_rowenc_totals;
+
+typedef struct pbl_rowenc_out {
+  uint8_t* blocks;             /* [blocks_cap] */
+  uint64_t* block_off;         /* [block_cap] */
+  uint32_t* block_len;         /* [block_cap] */
+  uint32_t* block_stream;      /* [block_cap] */
+  uint64_t* block_first_kv;    /* [block_cap] */
+  uint32_t* block_n_kv;        /* [block_cap] */
+  uint64_t* stream_block_base; /* [n_streams + 1] */
+  uint32_t* stream_status;     /* [n_streams] */
+  uint8_t* obsolete;           /* [n_kv], optional */
+  pbl_rowenc_totals* totals;   /* [1] */
+  uint64_t blocks_cap, block_cap;
+} pbl_rowenc_out;
+
+uint64_t pbl_rowenc_workspace_bytes(uint32_t n_streams, uint64_t n_kv);
+int pbl_rowenc_size(const pbl_rowenc_in* in, const pbl_rowenc_opts* opts, pbl_rowenc_out* out, void* workspace,
+                    uint64_t workspace_bytes, void* stream);
+int pbl_rowenc_batch(const pbl_rowenc_in* in, const pbl_rowenc_opts* opts, pbl_rowenc_out* out, void* workspace,
+                     uint64_t workspace_bytes, uint32_t flags, void* stream);
+/* The same rules over HOST arrays as the reference's sequential loop: one
+ * pbl_rowblk_writer per block and shouldFlush before every Add (a different
+ * algorithm from the device's scans, so that the two check each other).  No
+ * device call, no workspace.  Single-threaded. */
+int pbl_rowenc_batch_host(const pbl_rowenc_in* in, const pbl_rowenc_opts* opts, pbl_rowenc_out* out);
+/* sizeof(pbl_rowenc_opts), its 6 field offsets, sizeof(pbl_rowenc_in), its 4,
+ * sizeof(pbl_rowenc_totals), its 5, sizeof(pbl_rowenc_out), its 12 (the other
+ * layout lists are unchanged; ABI version 9 stands). */
+size_t pbl_rowenc_struct_layout(uint64_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

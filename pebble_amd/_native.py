@@ -257,6 +257,33 @@ class CompactOutC(ctypes.Structure):  # pbl_compact_out
                 ("n_ineffectual", _vp), ("n_nondeterministic", _vp)]
 
 
+# row-block encoder (pbl_rowenc_batch)
+PBL_ENC_VALUE_PREFIX, PBL_ENC_OBSOLETE, PBL_ENC_LOWEST_LEVEL = 0x1, 0x2, 0x4  # pbl_rowenc_opts.flags
+PBL_ROWENC_SIZED = 0x1  # pbl_rowenc_batch flags
+
+
+class RowEncOptsC(ctypes.Structure):  # pbl_rowenc_opts
+    _fields_ = [("restart_interval", ctypes.c_uint32), ("target_block_size", ctypes.c_uint32),
+                ("block_size_threshold", ctypes.c_uint32), ("comparer", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class RowEncInC(ctypes.Structure):  # pbl_rowenc_in
+    _fields_ = [("batch", DecodeOutC), ("n_streams", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("n_kv", ctypes.c_uint64)]
+
+
+class RowEncTotalsC(ctypes.Structure):  # pbl_rowenc_totals
+    _fields_ = [("n_blocks", ctypes.c_uint64), ("block_bytes", ctypes.c_uint64), ("n_restarts", ctypes.c_uint64),
+                ("status_mask", ctypes.c_uint32), ("n_bad_streams", ctypes.c_uint32)]
+
+
+class RowEncOutC(ctypes.Structure):  # pbl_rowenc_out
+    _fields_ = [("blocks", _vp), ("block_off", _vp), ("block_len", _vp), ("block_stream", _vp),
+                ("block_first_kv", _vp), ("block_n_kv", _vp), ("stream_block_base", _vp), ("stream_status", _vp),
+                ("obsolete", _vp), ("totals", _vp), ("blocks_cap", ctypes.c_uint64), ("block_cap", ctypes.c_uint64)]
+
+
 # range deletions in the read path (pbl_rangedel_set, pbl_rangedel_cover, the view's _rd entry points)
 PBL_RANGEDEL_MAX_RUNS = 16
 PBL_KIND_RANGEDEL = 15
@@ -431,6 +458,14 @@ SIGNATURES = {
     "pbl_compact_batch_host": (ctypes.c_int, [ctypes.POINTER(CompactInC), ctypes.POINTER(CompactOutC),
                                               ctypes.c_uint32]),
     "pbl_compact_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
+    "pbl_rowenc_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint64]),
+    "pbl_rowenc_size": (ctypes.c_int, [ctypes.POINTER(RowEncInC), ctypes.POINTER(RowEncOptsC),
+                                       ctypes.POINTER(RowEncOutC), _vp, ctypes.c_uint64, _vp]),
+    "pbl_rowenc_batch": (ctypes.c_int, [ctypes.POINTER(RowEncInC), ctypes.POINTER(RowEncOptsC),
+                                        ctypes.POINTER(RowEncOutC), _vp, ctypes.c_uint64, ctypes.c_uint32, _vp]),
+    "pbl_rowenc_batch_host": (ctypes.c_int, [ctypes.POINTER(RowEncInC), ctypes.POINTER(RowEncOptsC),
+                                             ctypes.POINTER(RowEncOutC)]),
+    "pbl_rowenc_struct_layout": (ctypes.c_size_t, [_vp, ctypes.c_size_t]),
     "pbl_abi_version": (ctypes.c_int, []),
     "pbl_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "pbl_workspace_bytes_for": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),

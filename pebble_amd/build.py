@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpebble_amd.so")
-SOURCES = ["rowblk_decode.hip", "colblk_decode.hip", "transforms.hip", "physical.hip", "zstd.hip", "sstable.hip", "seek.hip", "filter.hip", "scan.hip", "merge.hip", "visible.hip", "compact.hip", "rangedel.hip", "keyspan.hip", "rangekey.hip", "rowblk_writer.cpp", "colblk_writer.cpp", "zipf_gen.cpp", "data_iter.cpp"]
+SOURCES = ["rowblk_decode.hip", "colblk_decode.hip", "transforms.hip", "physical.hip", "zstd.hip", "sstable.hip", "seek.hip", "filter.hip", "scan.hip", "merge.hip", "visible.hip", "compact.hip", "rowenc.hip", "rangedel.hip", "keyspan.hip", "rangekey.hip", "rowblk_writer.cpp", "colblk_writer.cpp", "zipf_gen.cpp", "data_iter.cpp"]
 HEADERS = ["common.hip.h", "rowblk_core.hip.h", "rowblk_general.hip.h", "rowblk_big.hip.h", "rowblk_long.hip.h", "rowblk_pool.hip.h", "rowblk_wave.hip.h", "colblk_pipe.hip.h", "colblk_block.hip.h", "colblk_wave.hip.h", "zstd_dec.hip.h", "snappy_dec.hip.h", "minlz_dec.hip.h", "key_cmp.hip.h", "seek_core.hip.h", "filter_core.hip.h", "result_core.hip.h", "span_run.hip.h", os.path.join("..", "..", "include", "pebble_amd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-pthread"]

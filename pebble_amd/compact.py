@@ -10,8 +10,10 @@ numbers in the bottommost stripe (include/pebble_amd.h states the rules).  The
 result is a `DecodedBatch` again.  `compact_host()` runs the sequential loop
 over host arrays (pbl_compact_batch_host), the reference the device path is
 tested against.  `compact_tables()` is decode -> scan -> merge -> compact over
-several tables, the compaction-side sibling of `read()`.  torch is plumbing
-here: device memory and streams."""
+several tables, the compaction-side sibling of `read()`;
+`compact_tables_to_blocks()` adds the row-block encoder (pebble_amd.rowenc), so
+that what the compaction keeps leaves the device as data blocks.  torch is
+plumbing here: device memory and streams."""
 from __future__ import annotations
 
 import ctypes
@@ -166,3 +168,19 @@ def compact_tables(tables, lowers: Sequence[Optional[bytes]], uppers: Sequence[O
     merged = merge_scan(tables, lowers, uppers)
     return compact(merged.batch, comparer=comparer, snapshots=snapshots, elide_tombstones=elide_tombstones,
                    bottommost=bottommost)
+
+
+def compact_tables_to_blocks(tables, lowers: Sequence[Optional[bytes]], uppers: Sequence[Optional[bytes]], opts, *,
+                             snapshots=(), elide_tombstones: bool = False, bottommost: bool = False):
+    """`compact_tables`, then `rowenc.encode` of what it keeps: every range is
+    one stream, written as a fresh table writer with `opts` (a `RowEncOptions`;
+    its comparer must be the tables') would write it.  Returns (CompactResult,
+    EncodedBlocks): block b holds the result KVs block_first_kv[b] .. +
+    block_n_kv[b] of range block_stream[b]."""
+    from .rowenc import encode
+    tables = list(tables)
+    if opts.comparer != tables[0].comparer():
+        raise ValueError("compact_tables_to_blocks: the options' comparer is not the tables'")
+    res = compact_tables(tables, lowers, uppers, snapshots=snapshots, elide_tombstones=elide_tombstones,
+                         bottommost=bottommost)
+    return res, encode(res.batch, opts)
